@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the LPD-Net global-descriptor hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,12 @@ shard of clouds (the path shards by cloud, no data-path collective): weak scalin
 GPU over RCCL), passes rank 0's JSON line through and exits with the children's status.  Launched by torch.distributed.run
 directly (RANK set) it is a worker.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the kNN-aggregation kernel BASELINE.json names
+A plain run does what the headline needs and nothing else: set-up, settling and warm-up forwards, the K timed steps, the outputs of
+the last step when `--dump-outputs DIR` is given (DIR/descriptors.npy, the same seeded inputs in every run with the same arguments), and
+the line.  `--full` adds every other figure after the timed steps: the same K steps with one batch in flight, the per-op kernel table
+and rooflines, the secondary eval records, the train steps and the CPU baselines (the `--no-*` switches drop some of them).
+
+Prints ONE JSON line on rank 0.  With --full, `roofline` is for the kNN-aggregation kernel BASELINE.json names
 (edge_gather_max on the SN1 stage): algorithmic bytes = 3152 B/point / average launch
 time measured with HIP events on the launch stream inside the timed region.  `cpu_baseline` is the
 oracle (torch-CPU restatement of the reference path) timed on this box's host cores on a bounded
@@ -43,6 +48,19 @@ VALU_F32_PEAK_TF = 157.3       # fp32 vector peak (= f32-input MFMA peak): the b
 # SQ_VALU_MFMA_BUSY_CYCLES share of the kNN walk kernels, from the committed PMC table (not collected inside a bench run)
 KNN_MFMA_BUSY = {64: {"value": 0.29, "source": "profiles/r05_pmc_train_bf16_final.txt"}, 3: {"value": 0.05, "source": "profiles/r05_pmc_train_bf16_final.txt"}}
 LINE_MAX_BYTES = 4096          # the driver parses the final stdout line: it stays below this; everything else goes to bench_detail.json
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs writes at most this much in all (over all ranks)
+
+
+def dump_outputs(out_dir, name, t, max_bytes):
+    """--dump-outputs: the array the timed path handed its caller in the last step, as out_dir/<name>.npy in float32.  Larger than
+    max_bytes: a fixed, seeded sample of its rows (the same rows in every run with the same arguments), in their order."""
+    import numpy as np
+    a = t.detach().float().cpu().numpy()
+    row_bytes = a.nbytes // max(1, a.shape[0])
+    if a.nbytes > max_bytes:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], max_bytes // row_bytes, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_rooflines(kern, batch, points, k, split_bf16, knn_visits=None):
@@ -161,7 +179,7 @@ def compact_line(full, detail_name="bench_detail.json"):
         if isinstance(roof.get("stage"), dict):
             r["stage_frac_direct_form"] = roof["stage"].get("frac_direct_form")
         line["roofline"] = r
-    else:
+    elif "roofline" in full:
         line["roofline"] = None
     rk = full.get("roofline_kernels") or {}
     if rk:
@@ -204,7 +222,8 @@ def compact_line(full, detail_name="bench_detail.json"):
             else:                       # one level of nesting (operating points, storage variants): ms per step only
                 short[name[:40]] = {str(k_)[:16]: v_.get("ms_per_step") for k_, v_ in rec.items() if isinstance(v_, dict)}
         line["secondary"] = short
-    line["detail"] = detail_name
+    if detail_name:
+        line["detail"] = detail_name
     # size guard: the optional blocks go first, the contract's keys never
     for drop in ("secondary", "roofline_kernels", "descriptors_per_s_per_rank"):
         if len(json.dumps(line)) < LINE_MAX_BYTES - 64:
@@ -231,8 +250,15 @@ def parse():
                          "steps are enqueued on this many HIP streams; 1 = one after the other (also measured, reported beside the headline)")
     ap.add_argument("--points", type=int, default=4096)
     ap.add_argument("--k", type=int, default=20, help="neighbours per point (reference hard-codes 20; configs[4] uses 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary quadruplet train-step measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the K timed steps, also measure everything beside the headline: the same steps with one batch in flight, "
+                         "the per-op kernel table and rooflines, the secondary eval records, the train steps and the CPU baselines "
+                         "(the line gains their figures, the whole record goes to bench_detail.json).  Without it a run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the descriptors of the last timed step to DIR/descriptors.npy (float32; with N > 1 ranks, "
+                         "DIR/descriptors_rank<r>.npy per rank)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the secondary quadruplet train-step measurement")
     ap.add_argument("--train-steps", type=int, default=10)
     ap.add_argument("--no-train-bf16", action="store_true", help="skip the bf16-storage train-step measurement (configs[2] as stated)")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
@@ -240,8 +266,11 @@ def parse():
                          "visible (ranks share them: RCCL refuses two ranks on one device): launcher, exchange block and per-rank "
                          "reporting execute, the line is marked dry_run and its timings mean nothing")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary eval records (configs[1] at 128 clouds/step, configs[4]: N=16384, k=64, 64 clouds/step)")
-    return ap.parse_args()
+                    help="with --full: skip the secondary eval records (configs[1] at 128 clouds/step, configs[4]: N=16384, k=64, 64 clouds/step)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def visible_gpus():
@@ -742,34 +771,39 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # ---- a second timed region with ONE batch in flight (the latency view), its K-agg launches (the roofline kernel) bracketed by HIP
-    # events on the launch stream.  Only those: bracketing all ~45 launches of a step costs 1.6 ms of host time per step (event creation +
-    # two records per call) and made the host, not the GPU, the bottleneck of the timed region in some runs.
-    for i in range(4):
-        step_single(i)
-    ops.PROFILE, ops.PROFILE_ONLY = {}, ("edge_gather_max",)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        step_single(i)
-    torch.cuda.synchronize()
-    elapsed_single = time.perf_counter() - t1
-    gc.enable()
-    prof = ops.PROFILE
-    step = step_single                                   # (the per-op pass and the parity forward below: plain forwards)
-    # the per-op table of the detail record comes from a separate, untimed pass with every launch bracketed (HIP events on the launch
-    # stream) and the second stream switched off, so the entries are clean per-op durations
-    ops.PROFILE, ops.PROFILE_ONLY = {}, None
-    engine._SIDE_FORCE.mode = False          # this pass on ONE stream: clean per-op durations (the timed region runs the product's two)
-    try:
-        for i in range(min(args.steps, 5) + 1):
-            step(i)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "descriptors" if world == 1 else f"descriptors_rank{rank}", out, DUMP_MAX_BYTES // world)
+    if args.full:
+        # ---- a second timed region with ONE batch in flight (the latency view), its K-agg launches (the roofline kernel) bracketed by HIP
+        # events on the launch stream.  Only those: bracketing all ~45 launches of a step costs 1.6 ms of host time per step (event creation +
+        # two records per call) and made the host, not the GPU, the bottleneck of the timed region in some runs.
+        for i in range(4):
+            step_single(i)
+        ops.PROFILE, ops.PROFILE_ONLY = {}, ("edge_gather_max",)
         torch.cuda.synchronize()
-    finally:
-        engine._SIDE_FORCE.mode = None
-    prof_all = ops.PROFILE
-    prof_all.update({k_: v for k_, v in prof.items()})      # K-agg entries: the timed region's own measurements
-    ops.PROFILE = None
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            step_single(i)
+        torch.cuda.synchronize()
+        elapsed_single = time.perf_counter() - t1
+        gc.enable()
+        prof = ops.PROFILE
+        step = step_single                                   # (the per-op pass and the parity forward below: plain forwards)
+        # the per-op table of the detail record comes from a separate, untimed pass with every launch bracketed (HIP events on the launch
+        # stream) and the second stream switched off, so the entries are clean per-op durations
+        ops.PROFILE, ops.PROFILE_ONLY = {}, None
+        engine._SIDE_FORCE.mode = False          # this pass on ONE stream: clean per-op durations (the timed region runs the product's two)
+        try:
+            for i in range(min(args.steps, 5) + 1):
+                step(i)
+            torch.cuda.synchronize()
+        finally:
+            engine._SIDE_FORCE.mode = None
+        prof_all = ops.PROFILE
+        prof_all.update({k_: v for k_, v in prof.items()})      # K-agg entries: the timed region's own measurements
+        ops.PROFILE = None
+    else:
+        gc.enable()
     per_rank = [round(args.batch * args.steps / my_elapsed, 1)]
     if dist is not None:
         elapsed = _dist_max(dist, dev, elapsed)
@@ -781,7 +815,7 @@ def main():
     total_desc = args.batch * args.steps * world
     value = total_desc / elapsed
 
-    kern = kernel_table(prof_all)
+    kern = kernel_table(prof_all) if args.full else {}      # (a plain run: no table, so no roofline entry below)
     roof = None
     key, kname = "edge_gather_max16[C=256]", "edge_gather_max_cloud16p_kernel (persistent workgroups, LDS-resident cloud slice)"
     if key not in kern:     # k != 20 or N > 4096
@@ -838,7 +872,7 @@ def main():
                              "frac_direct_form": round(alg_direct / t_stage / 1e9 / HBM_PEAK_GBS, 4)}
 
     secondary = None
-    if world == 1 and not args.no_secondary and (args.points, args.k, args.batch) == (4096, 20, 32):
+    if args.full and world == 1 and not args.no_secondary and (args.points, args.k, args.batch) == (4096, 20, 32):
         # configs[1] "run both" batch sizes (evaluate.py:101-102 multiplies eval_batch_size by 1+P+Ng), and the
         # stress configuration configs[4] with its K-agg roofline, so that neither is builder-run only
         # (128 clouds run as four slices, two of them in flight: an event pair around a launch would span its wait for CUs -- no K-agg figure here)
@@ -856,7 +890,7 @@ def main():
                                  if kk in ("value", "unit", "ms_per_step", "steps")}
             for b in (1, 2, 6, 10, 24)}
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         del out
         torch.cuda.empty_cache()
         train = train_bench(dev, dist, world, rank, args.points, args.train_steps)
@@ -878,7 +912,7 @@ def main():
                      if kk in ("value", "unit", "ms_per_step", "steps", "config", "losses", "peak_hbm_gib")}
                 for st in ("f32", "bf16")}
 
-    knn_visits = knn_visit_stats(model, clouds[0]) if rank == 0 else None
+    knn_visits = knn_visit_stats(model, clouds[0]) if args.full and rank == 0 else None
     if rank == 0:
         line = {
             "metric": "global descriptors/sec (4096-pt clouds)", "value": round(value, 2), "unit": "descriptors/s",
@@ -898,18 +932,20 @@ def main():
                                       "products as 3-product split-bf16 MFMA with fp32 accumulation (DESIGN.md 3.2)"
                                       if ops.GEMM_BF16X3 else "fp32 tensors, every product on the f32-input MFMA / fp32 FMA")},
             "descriptors_per_s_per_rank": per_rank,
-            "one_batch_in_flight": {"value": round(args.batch * args.steps / elapsed_single, 2), "unit": "descriptors/s per GPU",
-                                    "ms_per_step": round(1e3 * elapsed_single / args.steps, 3),
-                                    "note": "the same K steps one after the other on one stream pair (rank 0): the latency of one batch; "
-                                            "the roofline kernel's HIP-event time comes from this region"},
-            "roofline": roof, "roofline_kernels": kernel_rooflines(kern, args.batch, args.points, args.k, ops.GEMM_BF16X3, knn_visits),
-            "kernels": kern, "train": train,
         }
+        if args.full:
+            line.update({
+                "one_batch_in_flight": {"value": round(args.batch * args.steps / elapsed_single, 2), "unit": "descriptors/s per GPU",
+                                        "ms_per_step": round(1e3 * elapsed_single / args.steps, 3),
+                                        "note": "the same K steps one after the other on one stream pair (rank 0): the latency of one batch; "
+                                                "the roofline kernel's HIP-event time comes from this region"},
+                "roofline": roof, "roofline_kernels": kernel_rooflines(kern, args.batch, args.points, args.k, ops.GEMM_BF16X3, knn_visits),
+                "kernels": kern, "train": train})
         if secondary is not None:
             line["secondary"] = secondary
         if train is not None and train_bf16 is not None:
             line["train_bf16"] = train_bf16
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, xs, ref, best_threads = cpu_baseline(model, args.points)
             with torch.no_grad():
                 got = model(xs.to(dev)).cpu()
@@ -923,17 +959,19 @@ def main():
                     train_bf16["cpu_baseline"] = tb
         # the full record (kernel tables, per-step arrays, secondary records, notes) goes to a side file and to stderr; stdout
         # carries ONE line below LINE_MAX_BYTES (the driver parses it: a 20 KB line was not parseable)
-        detail = json.dumps(line)
-        detail_name = "bench_detail.json" if world == 1 else f"bench_detail_n{world}.json"
-        for d_ in (ROOT, __import__("tempfile").gettempdir()):
-            try:
-                with open(os.path.join(d_, detail_name), "w") as f_:
-                    f_.write(detail + "\n")
-                break
-            except OSError:
-                continue
-        sys.stderr.write("bench detail: " + detail + "\n")
-        sys.stderr.flush()
+        detail_name = None                  # (a plain run: the line is the whole record)
+        if args.full:
+            detail = json.dumps(line)
+            detail_name = "bench_detail.json" if world == 1 else f"bench_detail_n{world}.json"
+            for d_ in (ROOT, __import__("tempfile").gettempdir()):
+                try:
+                    with open(os.path.join(d_, detail_name), "w") as f_:
+                        f_.write(detail + "\n")
+                    break
+                except OSError:
+                    continue
+            sys.stderr.write("bench detail: " + detail + "\n")
+            sys.stderr.flush()
         short = json.dumps(compact_line(line, detail_name))
         assert len(short) < LINE_MAX_BYTES, len(short)
         line_out.write(short + "\n")

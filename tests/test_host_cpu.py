@@ -308,6 +308,34 @@ def test_bench_stdout_line_stays_parseable():
     assert small["value"] == full["value"] and small["roofline"]["frac"] == 0.5363
 
 
+def test_bench_plain_line_and_output_dump(tmp_path):
+    """A plain bench run (no --full) measures the headline alone: its line names no detail file and carries no roofline block.
+    --dump-outputs writes the last step's descriptors as float32 .npy; an array above the byte budget is cut to a fixed, seeded
+    sample of its rows (in order), the same rows in every run."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    head = {"metric": "global descriptors/sec (4096-pt clouds)", "value": 19000.0, "unit": "descriptors/s", "n_gpus": 1, "steps": 20,
+            "warmup": 3, "ms_per_step": 1.684, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic", "config": {"workload": "BASELINE configs[1]"}, "descriptors_per_s_per_rank": [19000.0]}
+    line = bench.compact_line(head, None)
+    assert "detail" not in line and "roofline" not in line and "train" not in line and "cpu_baseline" not in line
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[key] == head[key], key
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    d = torch.randn(32, 256, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), "descriptors", d, bench.DUMP_MAX_BYTES)
+    got = np.load(tmp_path / "a" / "descriptors.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, d.float().numpy())
+    big = torch.arange(1000 * 256, dtype=torch.float32).view(1000, 256)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), "descriptors", big, 100 * 256 * 4)
+    b, c = np.load(tmp_path / "b" / "descriptors.npy"), np.load(tmp_path / "c" / "descriptors.npy")
+    assert b.shape == (100, 256) and np.array_equal(b, c)
+    rows = (b[:, 0] / 256).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b, big.numpy()[rows])
+
+
 def test_header_marks_superseded_entry_points_and_debug_switches_are_one_variable():
     """include/lpd_hip.h lists the entry points that are not on a default path (measured by tools/abi_coverage.py): every name it lists
     is a declared entry point.  The A/B ablation switches are ONE environment variable (LPD_DEBUG, lpdnet_hip/_debug.py + lpd_debug()

@@ -117,14 +117,14 @@ def test_grad_allreduce_world2_real_model_one_gpu(cuda, tmp_path):
 
 
 def test_bench_two_ranks_dry_run_over_gloo_on_one_gpu(cuda):
-    """`python bench.py --gpus 2 --dist-backend gloo`: the whole multi-rank code path of the bench on the box's one GPU (RCCL
+    """`python bench.py --full --gpus 2 --dist-backend gloo`: the whole multi-rank code path of the bench on the box's one GPU (RCCL
     refuses two ranks on one device, so gloo carries the collectives) -- the launcher starts the ranks as a child process tree
     without touching the GPU itself, every rank embeds its own shard, the train leg runs under GradAllReduce and fills the
     `exchange` block, rank 0 prints ONE JSON line with n_gpus = 2, a per-rank list of two and the dry-run mark.  No timing in it is
     asserted or means anything (two ranks share one GPU)."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
            "--batch", "4", "--points", "1024", "--train-steps", "1", "--no-train-bf16", "--no-cpu-baseline", "--no-secondary",
            "--settle-seconds", "0", "--settle-max-seconds", "0"]
     env = dict(os.environ)
@@ -147,3 +147,35 @@ def test_bench_two_ranks_dry_run_over_gloo_on_one_gpu(cuda):
     for key in ("allreduce_ms_per_step_isolated", "allreduce_busbw_GBps", "ms_per_step_without_exchange", "allreduce_exposed_ms_per_step"):
         assert key in ex
     assert "gloo" in ex["backend"] and full["train"]["tuples_per_s"] > 0 and full["value"] == rec["value"]
+
+
+def test_bench_plain_run_dumps_the_same_descriptors_every_run(cuda, tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: ONE line with the headline alone (no detail file, no roofline, train,
+    secondary or CPU-baseline block), its K steps as asked, and DIR/descriptors.npy = the last timed step's descriptors, the same in a
+    second run with the same arguments (seeded clouds and weights; 2e-6: the NetVLAD column sums are float atomics), so that two
+    builds can be compared output for output."""
+    import json
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--points", "1024",
+               "--settle-seconds", "0", "--settle-max-seconds", "0", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and rec["unit"] == "descriptors/s" and rec["dtype"] == "f32"
+        assert rec["higher_is_better"] is True and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 4 * 1e3 / rec["ms_per_step"]) < 0.01 * rec["value"]
+        for key in ("detail", "roofline", "roofline_kernels", "one_batch_in_flight", "train", "train_bf16", "secondary", "cpu_baseline"):
+            assert key not in rec, key
+        d = np.load(tmp_path / run / "descriptors.npy")
+        assert d.shape == (4, 256) and d.dtype == np.float32 and np.isfinite(d).all() and np.abs(d).max() > 0
+        assert os.listdir(tmp_path / run) == ["descriptors.npy"]
+        outs.append(d)
+    assert np.abs(outs[0] - outs[1]).max() <= 2e-6 * np.abs(outs[1]).max()

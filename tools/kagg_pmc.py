@@ -45,7 +45,7 @@ def one_pass(tag, counters, bench_args):
     os.makedirs(d, exist_ok=True)
     env = dict(os.environ, LPD_SIDE_STREAM="0", TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "--pmc"] + counters + ["-d", d, "-o", "p", "--", "python3",
-           os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-train", "--no-cpu-baseline", "--no-secondary"] + bench_args
+           os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-train", "--no-cpu-baseline", "--no-secondary"] + bench_args
     r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(f"rocprofv3 pass {tag} failed:\n{r.stderr[-2000:]}")
