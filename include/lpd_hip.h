@@ -365,6 +365,30 @@ int lpd_retrieval_topk(const float* S, const float* Q, int ldq, const float* D, 
                        int32_t* idx, float* dist, float* ws, void* stream);
 
 /*
+ * The recall evaluation of evaluate.py:33-93 (every (database run m, query run n) pair scored as in get_recall, evaluate.py:162-206)
+ * in one launch over resident descriptor tables; the n_q x n_db score matrices are never stored.  Distances, ranking and ties are
+ * those of lpd_retrieval_topk (exact f32-input MFMA dot products, fmaf-chain norms, max(|q|^2 + |d|^2 - 2 q.d, 0), ties -> lower index).
+ *   Q [q_rows][ldq]: every query run concatenated, run n = rows q_off[n] .. q_off[n+1]; D [d_rows][ldd] likewise with d_off [rd+1]
+ *   (q_off[0] = d_off[0] = 0; dim = 64, 128 or 256, ldq / ldd multiples of 4, 16-byte aligned tables: pad other descriptor sizes
+ *   with zero channels, which change no result).  pairs [npairs][2] int32 = (m, n), npairs <= 65535.  Pair p's queries own the output rows
+ *   out_off[p] .. out_off[p+1] (= the pair offsets, out_off[p+1] - out_off[p] = Nq of run n); max_qtiles = max over pairs of
+ *   ceil(Nq / 128).  Truth lists as CSR: the list QUERY_SETS[n][i][m] of global query row g = q_off[n] + i is
+ *   truth_idx[truth_off[g * rd + m] .. truth_off[g * rd + m + 1]) (row numbers inside run m).
+ *   k <= 64; pair p ranks its k_p = min(k, Nd of run m) nearest rows.  Per (pair, query) row:
+ *     first    int32: -1 = no truth in run m (not evaluated); k = no true neighbour within the k_p ranks; else the first rank that holds one
+ *     one_pct  uint8: a true neighbour within the first min(max(round(Nd / 100), 1), k_p) ranks (round half to even, as Python's round)
+ *     top1_sim fp32: dot product of the query with its rank-0 row (the top-1 similarity where first == 0)
+ *     topk_idx int32 [k] (optional, NULL = not written): the ranked row numbers inside run m, -1 past k_p
+ *   per pair: hist [npairs][k+1] (queries whose first hit is at rank r; column k = not found), n_eval [npairs] (evaluated queries),
+ *   n_onepct [npairs] (one-percent hits) -- overwritten.  ws: q_rows + d_rows floats (the squared norms).  The caller guarantees that the
+ *   offsets, pairs and truth_off index inside the tables (lpdnet_hip/ops.py recall_pairs checks them on the host).
+ */
+int lpd_recall_pairs(const float* Q, int ldq, const float* D, int ldd, int dim, const int32_t* q_off, const int32_t* d_off, int rd,
+                     int q_rows, int d_rows, const int32_t* pairs, const int32_t* out_off, int npairs, int max_qtiles,
+                     const int32_t* truth_off, const int32_t* truth_idx, int k, int32_t* first, uint8_t* one_pct, float* top1_sim,
+                     int32_t* topk_idx, int32_t* hist, int32_t* n_eval, int32_t* n_onepct, float* ws, void* stream);
+
+/*
  * Batched hard-negative selection (util/data.py:103-115, called for every item of the second training phase with 4000 sampled
  * negatives: a KDTree per query there): for query b, among the rows cand[b][0..nc) of the latent-vector table, the k nearest to
  * Q[b] by squared Euclidean distance, nearest first, as POSITIONS into cand[b] (ties -> lower position); dist [bq][k].

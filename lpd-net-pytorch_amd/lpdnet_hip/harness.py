@@ -11,6 +11,9 @@ AROUND the model call, with plain arguments:
 and the two "next" rows of SURVEY.md section 8f that sit right behind them:
   get_recall         evaluate.py:162-206             Recall@N / top-1 similarity / one-percent recall of one (database run,
                                                      query run) pair; the KDTree per pair becomes one GPU top-k launch
+  evaluate_model     evaluate.py:33-93               the whole evaluation: every run embedded into one resident table (embed_runs),
+                                                     every (m, n) pair scored in ONE lpd_recall_pairs launch (evaluate_pairs), the
+                                                     reference's aggregation on the host
   get_random_hard_negatives  util/data.py:103-115    the hard_neg_num nearest of the sampled negatives of a query (KDTree over 4000
                                                      latent vectors per item there; one GPU top-k launch here)
   save_checkpoint /  train_pointnetvlad.py:64-77,    the reference's .ckpt dict (epoch, iter, state_dict, optimizer, recall)
@@ -199,6 +202,202 @@ def get_recall(m, n, DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num=REC
     one_percent_recall = (one_percent_retrieved / float(num_evaluated)) * 100
     recall = (np.cumsum(recall) / float(num_evaluated)) * 100
     return recall, top1_similarity_score, one_percent_recall
+
+
+def _cuda_device_or_raise(what, device=None):
+    if not torch.cuda.is_available():
+        from ._lib import LpdHipError
+        raise LpdHipError(f"{what}: no GPU visible; the recall evaluation runs on the MI355X only (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _embed_batches(model, batches, dev):
+    """model(batch) for every batch of the iterable in eval mode, PIPELINE_IN_FLIGHT batches on the GPU at once; -> list of outputs
+    (valid on the caller's stream).  The caller restores the train/eval mode."""
+    model.eval()
+    pipe = BatchPipeline(model, PIPELINE_IN_FLIGHT if torch.device(dev).type == "cuda" else 1, dev)
+    outs = [pipe.submit(b) for b in batches]
+    pipe.join()
+    return outs
+
+
+def embed_runs(model, runs, batch_size):
+    """Descriptors of several runs as ONE resident table: runs = list of [n_r, N, 3] array-likes (float64 like the .bin submaps, or
+    float32), each embedded as get_latent_vectors does (batches of `batch_size`, ragged tail, eval mode, BatchPipeline) but nothing
+    comes back to the host.  -> (table CUDA fp32 [sum n_r, D], offsets numpy int64 [len(runs) + 1]); run r = rows offsets[r] ..
+    offsets[r + 1].  The model's train/eval mode is restored.  An empty run raises ValueError."""
+    dev = next(model.parameters()).device
+    runs = [np.asarray(r) for r in runs]
+    for i, r in enumerate(runs):
+        if r.ndim != 3 or r.shape[0] == 0 or r.shape[2] != 3:
+            raise ValueError(f"embed_runs: run {i} must be a non-empty [n, N, 3] array, got shape {r.shape}")
+    counts = np.array([r.shape[0] for r in runs], dtype=np.int64)
+
+    def batches():
+        for r in runs:
+            for s in range(0, r.shape[0], batch_size):
+                yield torch.from_numpy(np.ascontiguousarray(r[s:s + batch_size])).float().unsqueeze(1).to(dev)
+    was_training = model.training
+    try:
+        outs = _embed_batches(model, batches(), dev)
+    finally:
+        model.train(was_training)
+    offsets = np.zeros(len(runs) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return torch.cat([o.reshape(o.shape[0], -1) for o in outs], 0).float(), offsets
+
+
+def all_pairs(runs):
+    """evaluate.py:57-60: every (database run m, query run n) with m != n, m outer -> int32 [runs * (runs - 1), 2]"""
+    m, n = np.meshgrid(np.arange(runs), np.arange(runs), indexing="ij")
+    keep = m != n
+    return np.stack([m[keep], n[keep]], 1).astype(np.int32)
+
+
+def build_truth_csr(QUERY_SETS, q_counts, n_db_runs, pairs):
+    """The truth lists of an evaluation as ONE CSR table (what lpd_recall_pairs reads): the list QUERY_SETS[n][i][m] of global query
+    row g = sum(q_counts[:n]) + i is truth_idx[truth_off[g * n_db_runs + m] : truth_off[g * n_db_runs + m + 1]].  Only the (n, m) run
+    combinations that appear in `pairs` ([P, 2] rows (m, n)) are read; the others stay empty.  Lists may be Python lists or numpy
+    arrays (empty ones: the query is not evaluated in that run).  -> (truth_off int32 [sum(q_counts) * n_db_runs + 1], truth_idx int32)."""
+    import itertools
+    q_counts = [int(c) for c in q_counts]
+    need = np.zeros((len(q_counts), n_db_runs), dtype=bool)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    need[pairs[:, 1], pairs[:, 0]] = True
+    empty = ()
+
+    def lists():
+        for n, cnt in enumerate(q_counts):
+            want = need[n]
+            if not want.any():                           # a query run no pair reads: its entries are never touched
+                yield from itertools.repeat(empty, cnt * n_db_runs)
+                continue
+            run = QUERY_SETS[n]
+            for i in range(cnt):
+                entry = run[i]
+                for m in range(n_db_runs):
+                    yield entry[m] if want[m] else empty
+    total = sum(q_counts) * n_db_runs
+    seqs = list(lists())                                   # one walk over the nested structure
+    lens = np.fromiter(map(len, seqs), dtype=np.int64, count=total)
+    truth_off = np.zeros(total + 1, dtype=np.int64)
+    np.cumsum(lens, out=truth_off[1:])
+    if truth_off[-1] >= 2 ** 31:
+        raise ValueError("build_truth_csr: more than 2^31 truth entries")
+    idx = np.fromiter(itertools.chain.from_iterable(seqs), dtype=np.int64, count=int(truth_off[-1]))
+    return truth_off.astype(np.int32), idx.astype(np.int32)
+
+
+def recall_curves(hist, n_eval, n_onepct, recall_num=RECALL_NUM):
+    """Per-pair results of get_recall (evaluate.py:162-206) from the integer counts of lpd_recall_pairs, in float64 with the
+    reference's expressions: hist [P, >= recall_num] (queries whose first true neighbour is at rank r; the columns past the pair's
+    k are zero or the not-found count and are not read), n_eval [P], n_onepct [P].
+    -> (recall [P, recall_num] cumulative percent, one_percent_recall [P]).  A pair without an evaluated query raises
+    ZeroDivisionError, as the reference's `/ float(num_evaluated)` does."""
+    hist = np.asarray(hist, dtype=np.int64)
+    n_eval = np.asarray(n_eval, dtype=np.int64).reshape(-1)
+    if (n_eval == 0).any():
+        raise ZeroDivisionError(f"float division by zero (pair {int(np.argmax(n_eval == 0))} has no query with true neighbours)")
+    ev = n_eval.astype(np.float64)
+    recall = (np.cumsum(hist[:, :recall_num], axis=1) / ev[:, None]) * 100
+    one = (np.asarray(n_onepct, dtype=np.int64).reshape(-1) / ev) * 100
+    return recall, one
+
+
+def aggregate_evaluation(recall, one_percent_recall, similarities):
+    """evaluate.py:62-90 from the per-pair results: ave_recall = mean over the recall_num ranks of (sum of the pair curves, added in
+    pair order) / pair count -- a scalar, as the reference computes it; average_similarity_score = mean of every rank-0 similarity;
+    ave_one_percent_recall = mean of the per-pair one-percent recalls."""
+    recall = np.asarray(recall, dtype=np.float64)
+    count = recall.shape[0]
+    total = np.cumsum(recall, axis=0)[-1]                  # recall += pair_recall, one pair after the other
+    ave_recall = np.mean(np.mean(total / count))
+    average_similarity_score = np.mean(np.asarray(similarities, dtype=np.float64))
+    ave_one_percent_recall = np.mean(np.asarray(one_percent_recall, dtype=np.float64))
+    return ave_recall, average_similarity_score, ave_one_percent_recall
+
+
+def _resident(vectors, dev, name):
+    """a list of per-run descriptor arrays / tensors, or (CUDA table, offsets) -> (CUDA fp32 table, offsets numpy int64)"""
+    if (isinstance(vectors, tuple) and len(vectors) == 2 and isinstance(vectors[0], torch.Tensor) and vectors[0].dim() == 2
+            and np.asarray(vectors[1]).ndim == 1):
+        table, off = vectors
+        off = np.asarray(off, dtype=np.int64)
+        return table.to(dev, torch.float32), off
+    runs = [v.detach().float().to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+            for v in vectors]
+    for i, r in enumerate(runs):
+        if r.dim() != 2:
+            raise ValueError(f"{name}[{i}]: expected [n, D] descriptors, got shape {tuple(r.shape)}")
+    off = np.zeros(len(runs) + 1, dtype=np.int64)
+    np.cumsum([r.shape[0] for r in runs], out=off[1:])
+    return torch.cat(runs, 0), off
+
+
+def _evaluate_counts(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num, pairs, device=None):
+    from . import ops
+    dev = _cuda_device_or_raise("evaluate", device)
+    if not 1 <= recall_num <= ops.RECALL_KMAX:
+        raise ValueError(f"evaluate: recall_num={recall_num} (1..{ops.RECALL_KMAX} on the fused kernel; get_recall takes any)")
+    D, d_off = _resident(DATABASE_VECTORS, dev, "DATABASE_VECTORS")
+    Q, q_off = _resident(QUERY_VECTORS, dev, "QUERY_VECTORS")
+    pairs = all_pairs(len(QUERY_SETS)) if pairs is None else np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    for what, off, col in (("database", d_off, 0), ("query", q_off, 1)):
+        runs = off.size - 1
+        if pairs.size and (pairs[:, col].min() < 0 or pairs[:, col].max() >= runs):
+            raise ValueError(f"evaluate: a pair names {what} run outside the {runs} given")
+        empty = np.nonzero(np.diff(off)[pairs[:, col]] == 0)[0]
+        if empty.size:
+            raise ValueError(f"evaluate: {what} run {int(pairs[empty[0], col])} is empty")
+    truth_off, truth_idx = build_truth_csr(QUERY_SETS, np.diff(q_off), d_off.size - 1, pairs)
+    r = ops.recall_pairs(Q, D, q_off.astype(np.int32), d_off.astype(np.int32), pairs, truth_off, truth_idx, recall_num)
+    first, sim = r.first.cpu().numpy(), r.top1_sim.cpu().numpy()
+    return (r.hist.cpu().numpy(), r.n_eval.cpu().numpy(), r.n_onepct.cpu().numpy(), first, sim, r.out_off)
+
+
+def evaluate_pairs(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num=RECALL_NUM, pairs=None, device=None):
+    """get_recall (evaluate.py:162-206) for many (database run m, query run n) pairs in ONE launch (lpd_recall_pairs): no score
+    matrix, no per-pair uploads, the truth lists turned into one CSR table once.
+
+    DATABASE_VECTORS / QUERY_VECTORS: lists of per-run [n, D] descriptors (numpy, as get_latent_vectors returns them, or tensors), or
+    a resident (CUDA table, run offsets) tuple as embed_runs returns it.  QUERY_SETS[n][i][m] = true neighbours of query i of run n in
+    run m.  pairs: rows (m, n); default every m != n over range(len(QUERY_SETS)), m outer (the reference's loop order).
+    -> list, one entry per pair: (recall [recall_num] cumulative percent, top-1 similarity list, one-percent recall), identical to
+    get_recall(m, n, ...).
+
+    Edge cases: a pair whose queries have no true neighbours at all raises ZeroDivisionError (as the reference and get_recall do);
+    a database run shorter than recall_num is ranked to its length (k = n_db) and its curve still has recall_num entries; an empty run
+    raises ValueError; recall_num is at most 64; without a GPU the call raises (there is no CPU path, as for get_recall)."""
+    hist, n_eval, n_one, first, sim, out_off = _evaluate_counts(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num, pairs, device)
+    recall, one = recall_curves(hist, n_eval, n_one, recall_num)
+    top = first == 0
+    return [(recall[p], [float(v) for v in sim[out_off[p]:out_off[p + 1]][top[out_off[p]:out_off[p + 1]]]], float(one[p]))
+            for p in range(recall.shape[0])]
+
+
+def evaluate_from_descriptors(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num=RECALL_NUM, pairs=None, device=None):
+    """evaluate.py:33-93 after the embedding: -> (ave_recall, average_similarity_score, ave_one_percent_recall), aggregated on the
+    host in float64 from the integer counts of one lpd_recall_pairs launch (inputs and edge cases as evaluate_pairs)."""
+    hist, n_eval, n_one, first, sim, _ = _evaluate_counts(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num, pairs, device)
+    recall, one = recall_curves(hist, n_eval, n_one, recall_num)
+    return aggregate_evaluation(recall, one, sim[first == 0])
+
+
+def evaluate_model(model, database_sets, query_sets, QUERY_SETS, batch_size):
+    """evaluate.evaluate_model (evaluate.py:33-93) on clouds: database_sets / query_sets = lists of runs, each [n, N, 3] (float64 like
+    the .bin submaps, or float32); QUERY_SETS[n][i][m] the truth.  Every run is embedded into one resident table (embed_runs), every
+    (m, n) pair with m != n over range(len(QUERY_SETS)) scored in one launch (evaluate_pairs), and the results aggregated as the
+    reference does.  -> (ave_recall, average_similarity_score, ave_one_percent_recall); ave_recall is the mean of the summed recall
+    curve over all recall_num ranks (evaluate.py:73), not Recall@1.  The model is left in train mode (evaluate.py:156).
+    Edge cases as evaluate_pairs: ZeroDivisionError for a pair without evaluated queries, ValueError for an empty run, an error
+    without a GPU."""
+    _cuda_device_or_raise("evaluate_model")
+    try:
+        db = embed_runs(model, database_sets, batch_size)
+        qv = embed_runs(model, query_sets, batch_size)
+    finally:
+        model.train()
+    return evaluate_from_descriptors(db, qv, QUERY_SETS)
 
 
 def _unwrap(model):

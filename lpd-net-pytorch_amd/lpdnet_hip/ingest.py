@@ -7,6 +7,7 @@ host, and the host does no per-element work.
   load_pc_file / load_pc_files   loading_pointclouds.py:26-47, same return values (numpy float64)
   SubmapStream                   iterator over device batches [B,1,N,3] float32, double-buffered
   get_latent_vectors_from_files  evaluate.get_latent_vectors on a list of file names
+  evaluate_model_from_sets       evaluate.evaluate_model on the reference's pickled DATABASE_SETS / QUERY_SETS
 """
 import os
 
@@ -102,3 +103,39 @@ def get_latent_vectors_from_files(model, filenames, batch_size, dataset_folder="
     finally:
         model.train(was_training)
     return np.concatenate(outs, 0) if outs else np.zeros((0, output_dim), np.float32)
+
+
+def evaluate_model_from_sets(model, DATABASE_SETS, QUERY_SETS, batch_size, dataset_folder="", num_points=NUM_POINTS):
+    """evaluate.evaluate_model (evaluate.py:33-93) on the reference's pickled structures: DATABASE_SETS[r][i]["query"] and
+    QUERY_SETS[n][i]["query"] are submap file names (relative to dataset_folder), QUERY_SETS[n][i][m] the true neighbours of query i
+    of run n in run m.  Every run is streamed from disk through SubmapStream into the embedding pipeline and kept on the device as one
+    table; all (m, n) pairs, m != n, are scored in one lpd_recall_pairs launch (harness.evaluate_from_descriptors).
+    -> (ave_recall, average_similarity_score, ave_one_percent_recall); the model is left in train mode.
+
+    Files of the wrong size are skipped, exactly as load_pc_files skips them: the run's later descriptors then move up by one row,
+    while the truth lists still count the pickle's rows -- the reference's own indices shift the same way.  A run with no valid file
+    raises ValueError; edge cases otherwise as harness.evaluate_pairs."""
+    from . import harness
+    harness._cuda_device_or_raise("evaluate_model_from_sets")
+    dev = next(model.parameters()).device
+
+    def embed(sets, what):
+        tables, counts = [], []
+        for r, run in enumerate(sets):
+            files = [run[i]["query"] for i in range(len(run))]
+            outs = harness._embed_batches(model, SubmapStream(files, batch_size, dataset_folder, dev, num_points), dev)
+            n = sum(o.shape[0] for o in outs)
+            if n == 0:
+                raise ValueError(f"evaluate_model_from_sets: {what} run {r} has no submap of {num_points} points")
+            tables += [o.reshape(o.shape[0], -1) for o in outs]
+            counts.append(n)
+        off = np.zeros(len(counts) + 1, dtype=np.int64)
+        np.cumsum(counts, out=off[1:])
+        return torch.cat(tables, 0).float(), off
+
+    try:
+        db = embed(DATABASE_SETS, "database")
+        qv = embed(QUERY_SETS, "query")
+    finally:
+        model.train()
+    return harness.evaluate_from_descriptors(db, qv, QUERY_SETS)

@@ -1993,6 +1993,103 @@ def retrieval_topk(Q, D, k):
     return idx, dist
 
 
+RecallPairs = __import__("collections").namedtuple("RecallPairs", "first one_pct top1_sim hist n_eval n_onepct out_off topk_idx")
+RECALL_KMAX = 64
+
+
+def _index_array(x, name, ndim):
+    """int32 index array given as a numpy array or a (CPU or CUDA) tensor -> host numpy copy; ValueError on another dtype / rank"""
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.int32:
+            raise ValueError(f"{name}: expected int32, got {x.dtype}")
+        x = x.detach().cpu().numpy()
+    else:
+        import numpy as np
+        x = np.asarray(x)
+        if x.dtype != np.int32:
+            raise ValueError(f"{name}: expected int32, got {x.dtype}")
+    if x.ndim != ndim:
+        raise ValueError(f"{name}: expected {ndim}-D, got shape {x.shape}")
+    return x
+
+
+def _recall_table(X, name):
+    """descriptor table as lpd_recall_pairs reads it: 64 / 128 / 256 channels, rows 16-byte aligned (others: a zero-padded copy --
+    zero channels add nothing to the dot products or the norms)"""
+    ld = _rows(X, name)
+    dim = X.shape[1]
+    if dim > 256:
+        raise ValueError(f"recall_pairs: descriptors of {dim} channels (at most 256)")
+    dimp = 64 if dim <= 64 else (128 if dim <= 128 else 256)
+    if dim == dimp and ld % 4 == 0 and X.data_ptr() % 16 == 0:
+        return X, ld
+    Xp = torch.zeros((X.shape[0], dimp), dtype=torch.float32, device=X.device)
+    Xp[:, :dim] = X
+    return Xp, dimp
+
+
+def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=False):
+    """The recall evaluation of evaluate.py:33-93 in ONE launch (lpd_recall_pairs, include/lpd_hip.h): for every (database run m,
+    query run n) row of `pairs` and every query i of run n, the min(k, Nd_m) nearest rows of run m (squared L2 with the arithmetic of
+    retrieval_topk, ties -> lower index) scored against the truth list QUERY_SETS[n][i][m].
+
+    Q [sum Nq, dim], D [sum Nd, dim]: CUDA fp32, all runs concatenated (rows with a leading dimension allowed); q_off [Rq + 1],
+    d_off [Rd + 1]: run offsets (0 first); pairs [P, 2] = (m, n); truth_off [q_off[-1] * Rd + 1] / truth_idx: the truth lists as CSR
+    (list of global query row g and run m at truth_off[g * Rd + m]).  Index arrays: int32 numpy arrays or tensors (checked on the host).
+    -> RecallPairs: per (pair, query) row, pair p at rows out_off[p] .. out_off[p + 1] (query order):
+         first int32 (-1: no truth; k: no hit in the ranks; else the rank of the first true neighbour), one_pct uint8,
+         top1_sim fp32 (dot product with the rank-0 row), topk_idx int32 [.., k] (-1 past min(k, Nd); only with want_topk, else None);
+       per pair: hist int32 [P, k + 1] (column k = not found), n_eval int32 [P], n_onepct int32 [P]; out_off numpy int64 [P + 1]."""
+    import numpy as np
+    Q, ldq = _recall_table(Q, "Q")
+    D, ldd = _recall_table(D, "D")
+    if Q.shape[1] != D.shape[1]:
+        raise ValueError("recall_pairs: Q and D must share the descriptor size")
+    k = int(k)
+    if not 1 <= k <= RECALL_KMAX:
+        raise ValueError(f"recall_pairs: k={k} (1..{RECALL_KMAX})")
+    qo, do = _index_array(q_off, "q_off", 1), _index_array(d_off, "d_off", 1)
+    pr = _index_array(pairs, "pairs", 2)
+    to, ti = _index_array(truth_off, "truth_off", 1), _index_array(truth_idx, "truth_idx", 1)
+    for name, off, rows in (("q_off", qo, Q.shape[0]), ("d_off", do, D.shape[0])):
+        if off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] > rows:
+            raise ValueError(f"recall_pairs: {name} must rise from 0 to at most the {rows} table rows")
+    rq, rd = qo.size - 1, do.size - 1
+    if pr.shape[1] != 2 or not 1 <= pr.shape[0] <= 65535:
+        raise ValueError(f"recall_pairs: pairs must be [P, 2] with 1 <= P <= 65535, got {pr.shape}")
+    m, n = pr[:, 0].astype(np.int64), pr[:, 1].astype(np.int64)
+    if (m < 0).any() or (m >= rd).any() or (n < 0).any() or (n >= rq).any():
+        raise ValueError("recall_pairs: a pair names a run outside q_off / d_off")
+    nq, nd = (qo[n + 1] - qo[n]).astype(np.int64), (do[m + 1] - do[m]).astype(np.int64)
+    if (nq == 0).any() or (nd == 0).any():
+        raise ValueError("recall_pairs: a pair names an empty run")
+    if to.size != int(qo[-1]) * rd + 1 or to[0] != 0 or (np.diff(to) < 0).any() or to[-1] != ti.size:
+        raise ValueError("recall_pairs: truth_off must be [q_off[-1] * Rd + 1], rising from 0 to len(truth_idx)")
+    out_off = np.zeros(pr.shape[0] + 1, dtype=np.int64)
+    np.cumsum(nq, out=out_off[1:])
+    total, P = int(out_off[-1]), pr.shape[0]
+    if total >= 2 ** 31:
+        raise ValueError("recall_pairs: more than 2^31 (pair, query) rows")
+    dev = Q.device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev, non_blocking=False)   # noqa: E731
+    q_off_d, d_off_d, pairs_d, out_off_d, to_d = up(qo), up(do), up(pr), up(out_off), up(to)
+    ti_d = up(ti) if ti.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+    first = torch.empty((total,), dtype=torch.int32, device=dev)
+    one = torch.empty((total,), dtype=torch.uint8, device=dev)
+    sim = torch.empty((total,), dtype=torch.float32, device=dev)
+    topk = torch.empty((total, k), dtype=torch.int32, device=dev) if want_topk else None
+    hist = torch.empty((P, k + 1), dtype=torch.int32, device=dev)
+    n_eval = torch.empty((P,), dtype=torch.int32, device=dev)
+    n_one = torch.empty((P,), dtype=torch.int32, device=dev)
+    ws = torch.empty((int(qo[-1]) + int(do[-1]),), dtype=torch.float32, device=dev)
+    max_qtiles = int((nq.max() + 127) // 128)
+    lib = _lib.load()
+    _call("recall_pairs", lib.lpd_recall_pairs, _ptr(Q), ldq, _ptr(D), ldd, Q.shape[1], _ptr(q_off_d), _ptr(d_off_d), rd, int(qo[-1]),
+          int(do[-1]), _ptr(pairs_d), _ptr(out_off_d), P, max_qtiles, _ptr(to_d), _ptr(ti_d), k, _ptr(first), _ptr(one), _ptr(sim),
+          _ptr(topk), _ptr(hist), _ptr(n_eval), _ptr(n_one), _ptr(ws), _stream())
+    return RecallPairs(first, one, sim, hist, n_eval, n_one, out_off, topk)
+
+
 def hard_negatives(table, Q, cand, k):
     """For every query row Q[b]: the k rows of `table` nearest to it among cand[b] (int32 [bq, nc] row numbers), nearest first
     -> (positions into cand[b] int32 [bq, k], squared distances [bq, k]).  One launch for the whole batch."""

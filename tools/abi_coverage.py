@@ -116,6 +116,9 @@ d = torch.rand(50, 256, device=dev)
 ops.retrieval_topk(d[:10], d, 5)
 cand = torch.randint(0, 50, (4, 20), dtype=torch.int32, device=dev)
 ops.hard_negatives(d, d[:4].contiguous(), cand, 3)
+# the fused recall evaluation: 2 runs of 25 descriptors, both pairs in one launch
+harness.evaluate_pairs((d, np.array([0, 25, 50])), (d, np.array([0, 25, 50])),
+                       [[{0: [i], 1: [i]} for i in range(25)] for _ in range(2)])
 torch.cuda.synchronize()
 never = [n for n in _lib.SIGNATURES if counts[n] == 0]
 print(f"{len(_lib.SIGNATURES)} entry points bound; {len(_lib.SIGNATURES) - len(never)} called by the default runs; never called ({len(never)}):")
