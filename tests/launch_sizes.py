@@ -1,0 +1,111 @@
+"""Launch arithmetic of the size-dependent kernel paths, restated in Python, and the shapes at which the launch-size tests reach them.
+
+Several kernels change what they do with the launch size alone:
+  - the fused edge-MLP kernels (csrc/lpd_edge.hip em_tiles_per_block): a block walks ceil(tiles / 512) consecutive point tiles, at most 16,
+    so that one resident round of blocks covers the launch; the last block may get fewer tiles (the `m0 >= g.M` exit);
+  - the reduction kernels that end in fp64 atomics (csrc/lpd_common.h lpd_reduce_grid): at most 768 blocks, a grid-stride loop beyond;
+  - the BatchNorm-backward products on the transposed operand loader (csrc/lpd_train3.hip): at most 256 (fp32) / 512 (bf16) blocks.
+tests/test_launch_sizes_cpu.py checks every entry of the tables below against its stated regime, so a change of a heuristic shows which
+cases stop covering what they claim; tests/test_launch_sizes_gpu.py runs the kernels at these shapes.
+"""
+EM_ROUND = 512        # blocks of one resident round of the fused edge-MLP kernels (two per CU)
+EM_TMAX = 16          # most tiles a block walks (LPD_DEBUG=edge-mlp-tiles=n lowers it)
+REDUCE_CAP = 768      # lpd_reduce_grid (LPD_DEBUG=reduce-grid=n)
+
+
+def em_tiles_per_block(tiles, tmax=EM_TMAX):
+    t = (tiles + EM_ROUND - 1) // EM_ROUND
+    return max(1, min(t, tmax))
+
+
+def em_launch(M, pts, tmax=EM_TMAX):
+    """(tiles per block, grid, tiles of the last block) of a fused edge-MLP launch over M points in `pts`-point tiles"""
+    tiles = (M + pts - 1) // pts
+    t = em_tiles_per_block(tiles, tmax)
+    grid = (tiles + t - 1) // t
+    return t, grid, tiles - (grid - 1) * t
+
+
+def grid_for(items, per_block, cap=4096):
+    g = (items + per_block - 1) // per_block
+    return max(1, min(g, cap))
+
+
+def reduce_grid(wanted, cap=REDUCE_CAP):
+    return max(1, min(wanted, cap))
+
+
+def capped_launch(items, per_block, cap, gcap=4096):
+    """(blocks wanted, blocks launched, ragged): ragged = the grid-stride walk ends in a part-filled stride"""
+    wanted = grid_for(items, per_block, gcap)
+    grid = min(wanted, cap)
+    return wanted, grid, items % (grid * per_block) != 0
+
+
+# ---- fused edge MLP: eval (edge_mlp_x3: 64-point tiles, 32-point tiles with the x1 planes) and train backward (32-point tiles;
+# M % 32 == 0, and the gather pass of the backward needs N % 64 == 0 and k >= 16)
+EDGE_SHAPES = {
+    "t3": dict(B=5, N=8000, k=16),
+    "t16": dict(B=65, N=4160, k=16),
+}
+# name -> {form: (tiles per block, grid, tiles of the last block)}
+EDGE_REGIMES = {
+    "t3": {"bwd": (3, 417, 2), "x1": (3, 417, 2), "x3": (2, 313, 1)},
+    "t16": {"bwd": (16, 529, 2), "x1": (16, 529, 2), "x3": (9, 470, 4)},
+}
+EDGE_PTS = {"bwd": 32, "x1": 32, "x3": 64}
+
+
+def edge_launch(name, form, tmax=EM_TMAX):
+    s = EDGE_SHAPES[name]
+    return em_launch(s["B"] * s["N"], EDGE_PTS[form], tmax)
+
+
+# ---- reductions behind lpd_reduce_grid: rows per block of one grid-stride trip and the grid_for cap of each launch
+def reduce_launches(op, C, R):
+    """[(pass, items, per_block, grid_for cap)] of one call"""
+    if op == "colstats":
+        out, c0 = [], 0
+        while c0 < C:
+            w = 1024
+            while w > C - c0:
+                w >>= 1
+            out.append((f"colstats[{c0}:{c0 + w}]", R, (256 // (w // 4)) * 8, 4096))
+            c0 += w
+        return out
+    if op == "bn_act_bwd":
+        return [("reduce", R, (256 // (C // 4)) * 8, 4096), ("apply", R * (C // 4), 256 * 4, 4096)]
+    if op == "bn_act_bwd_bf16":
+        w = min(C, 1024)
+        panels = [(f"reduce[{c0}:{c0 + w}]", R, (256 // (w // 8)) * 8, 4096) for c0 in range(0, C, w)]
+        return panels + [("apply", R * (C // 8), 256 * 4, 4096)]
+    if op == "bn_sel_bwd_reduce":
+        return [("reduce", R, (256 // (C // 4)) * 4, 4096)]
+    if op == "edge_split_bwd":
+        return [("reduce", R, (256 // (C // 4)) * 8, 2048)]
+    raise KeyError(op)
+
+
+# (op, C, rows): every pass of every call launches more than REDUCE_CAP blocks' worth of work, with a ragged last stride
+REDUCE_ROWS = {64: 230_000, 128: 110_000, 1024: 14_000, 2048: 14_000}
+REDUCE_CASES = ([(op, C, REDUCE_ROWS[C]) for op in ("colstats", "bn_act_bwd", "bn_act_bwd_bf16", "bn_sel_bwd_reduce") for C in (64, 128, 1024)]
+                + [("bn_act_bwd_bf16", 2048, REDUCE_ROWS[2048])]
+                # lpd_edge_split_bwd is built for C in {64, 128, 256}: B clouds of 4096 points
+                + [("edge_split_bwd", 64, 25 * 4096), ("edge_split_bwd", 128, 13 * 4096), ("edge_split_bwd", 256, 7 * 4096)])
+# the same operators at small sizes, run under LPD_DEBUG=reduce-grid=7 (long grid-stride loops) and under the default cap
+REDUCE_SMALL_CAP = 7
+REDUCE_SMALL_CASES = [("colstats", 64, 5000), ("colstats", 1024, 1000), ("bn_act_bwd", 128, 3001), ("bn_act_bwd", 1024, 999),
+                      ("bn_act_bwd_bf16", 64, 6000), ("bn_act_bwd_bf16", 2048, 600), ("bn_sel_bwd_reduce", 128, 3001),
+                      ("bn_sel_bwd_reduce", 1024, 701), ("edge_split_bwd", 64, 3 * 1024), ("edge_split_bwd", 256, 2 * 1024)]
+
+# ---- the BatchNorm-backward products (E = M k rows of 32-row tiles): blocks = ceil(tiles / tiles per block), capped
+BNBWD = {"f32": (8, 256), "bf16": (4, 512)}      # (tiles per block, block cap)
+BNBWD_SHAPE = dict(M=30000, k=16)                 # E = 480 000 rows = 15 000 tiles: 7.3 / 7.3 strides, the last one part-filled
+
+
+def bnbwd_launch(mode, M, k):
+    tpb, cap = BNBWD[mode]
+    tiles = (M * k + 31) // 32
+    wanted = (tiles + tpb - 1) // tpb
+    grid = min(wanted, cap)
+    return wanted, grid, tiles % grid != 0

@@ -1,0 +1,47 @@
+"""The shapes of tests/test_launch_sizes_gpu.py reach the launch regimes they are there for (tests/launch_sizes.py restates the
+launch arithmetic of csrc/).  No GPU needed: if a heuristic changes, this names the cases that stop covering what they claim."""
+import pytest
+
+import launch_sizes as ls
+
+
+@pytest.mark.parametrize("name", sorted(ls.EDGE_SHAPES))
+def test_edge_mlp_shapes_reach_the_tile_loop(name):
+    s = ls.EDGE_SHAPES[name]
+    M = s["B"] * s["N"]
+    assert M % 32 == 0 and s["N"] % 64 == 0 and s["k"] >= 16            # the backward and its gather pass
+    for form, want in ls.EDGE_REGIMES[name].items():
+        t, grid, last = ls.edge_launch(name, form)
+        assert (t, grid, last) == want, (form, (t, grid, last))
+        assert t > 1 and 0 < last < t                                    # a tile loop whose last block runs short
+        assert ls.edge_launch(name, form, tmax=1)[0] == 1                # LPD_DEBUG=edge-mlp-tiles=1 turns it off
+    assert ls.edge_launch("t16", "bwd")[0] == ls.EM_TMAX and ls.edge_launch("t16", "bwd")[1] > ls.EM_ROUND   # the cap, past one round
+
+
+def test_em_tiles_per_block_mirror():
+    assert [ls.em_tiles_per_block(t) for t in (1, 256, 512, 513, 1024, 1025, 4096, 8192, 8193, 10 ** 6)] == [1, 1, 1, 2, 2, 3, 8, 16, 16, 16]
+    assert ls.em_launch(32 * 4096, 32) == (8, 512, 8)                   # B = 32 x 4096 at 32-point tiles: divides exactly
+    assert ls.em_launch(2 * 4096, 32) == (1, 256, 1)                    # the op tests' largest size (B = 2, N = 4096): no loop
+
+
+@pytest.mark.parametrize("op,C,R", ls.REDUCE_CASES)
+def test_reduction_shapes_pass_the_grid_cap(op, C, R):
+    for name, items, per_block, gcap in ls.reduce_launches(op, C, R):
+        wanted, grid, ragged = ls.capped_launch(items, per_block, ls.REDUCE_CAP, gcap)
+        assert grid == ls.REDUCE_CAP and wanted > ls.REDUCE_CAP and ragged, (name, wanted, grid, ragged)
+
+
+@pytest.mark.parametrize("op,C,R", ls.REDUCE_SMALL_CASES)
+def test_small_reduction_shapes_stride_under_the_debug_cap(op, C, R):
+    for name, items, per_block, gcap in ls.reduce_launches(op, C, R):
+        wanted, grid, ragged = ls.capped_launch(items, per_block, ls.REDUCE_SMALL_CAP, gcap)
+        assert grid == ls.REDUCE_SMALL_CAP and wanted >= 3 * ls.REDUCE_SMALL_CAP and ragged, (name, wanted, grid, ragged)
+        assert ls.capped_launch(items, per_block, ls.REDUCE_CAP, gcap)[1] < ls.REDUCE_CAP      # the default cap launches them whole
+
+
+@pytest.mark.parametrize("mode", sorted(ls.BNBWD))
+def test_bnbwd_product_shape_passes_its_cap(mode):
+    wanted, grid, ragged = ls.bnbwd_launch(mode, **ls.BNBWD_SHAPE)
+    tpb, cap = ls.BNBWD[mode]
+    assert grid == cap and ls.BNBWD_SHAPE["M"] * ls.BNBWD_SHAPE["k"] > 4 * cap * tpb * 32 and ragged
+    assert (ls.BNBWD_SHAPE["M"] * ls.BNBWD_SHAPE["k"]) % 32 == 0
