@@ -4,9 +4,11 @@ Several kernels change what they do with the launch size alone:
   - the fused edge-MLP kernels (csrc/lpd_edge.hip em_tiles_per_block): a block walks ceil(tiles / 512) consecutive point tiles, at most 16,
     so that one resident round of blocks covers the launch; the last block may get fewer tiles (the `m0 >= g.M` exit);
   - the reduction kernels that end in fp64 atomics (csrc/lpd_common.h lpd_reduce_grid): at most 768 blocks, a grid-stride loop beyond;
-  - the BatchNorm-backward products on the transposed operand loader (csrc/lpd_train3.hip): at most 256 (fp32) / 512 (bf16) blocks.
+  - the BatchNorm-backward products on the transposed operand loader (csrc/lpd_train3.hip): at most 256 (fp32) / 512 (bf16) blocks;
+  - the training-path kernels of csrc/lpd_train.hip (grid_for: at most 4096 blocks, a grid-stride loop beyond), the slice count of
+    lpd_vlad_finalize_bwd, the two paths of lpd_graph_transpose and the loops of lpd_dw_smallk.
 tests/test_launch_sizes_cpu.py checks every entry of the tables below against its stated regime, so a change of a heuristic shows which
-cases stop covering what they claim; tests/test_launch_sizes_gpu.py runs the kernels at these shapes.
+cases stop covering what they claim; tests/test_launch_sizes_gpu.py and tests/test_train_bwd_ops_gpu.py run the kernels at these shapes.
 """
 EM_ROUND = 512        # blocks of one resident round of the fused edge-MLP kernels (two per CU)
 EM_TMAX = 16          # most tiles a block walks (LPD_DEBUG=edge-mlp-tiles=n lowers it)
@@ -109,3 +111,69 @@ def bnbwd_launch(mode, M, k):
     wanted = (tiles + tpb - 1) // tpb
     grid = min(wanted, cap)
     return wanted, grid, tiles % grid != 0
+
+
+# ---- the training-path kernels of csrc/lpd_train.hip: grid_for caps every launch at GRID_CAP blocks and walks a grid-stride loop beyond
+GRID_CAP = 4096
+ACT_BLOCK = 4         # waves per block of the wave-per-point / wave-per-row kernels (edge_build, gather_sum_rows)
+
+
+def chain_launch(kernel, M, C):
+    """(blocks wanted, blocks launched, items, items per block and trip) of one launch of the materialised edge chain over M points of
+    C channels (C in 64 / 128 / 256); the grid-stride walk takes items / (launched * per trip) trips"""
+    q = C // 4
+    rg = 256 // q                          # rows per block and trip of the edge_bn_bwd kernels
+    if kernel == "edge_build":             # 64 / (C / 4) points per wave
+        items, per_block, per_trip = M, ACT_BLOCK * (64 // q), ACT_BLOCK * (64 // q)
+    elif kernel in ("group_max", "group_sum"):      # one thread per (point, column quad)
+        items, per_block, per_trip = M * q, 256, 256
+    elif kernel == "edge_bn_bwd_reduce":   # grid_for(M, 2 RG): two trips per block by design
+        items, per_block, per_trip = M, 2 * rg, rg
+    elif kernel == "edge_bn_bwd_apply":
+        items, per_block, per_trip = M, rg, rg
+    elif kernel == "gather_sum_rows":      # 256 / C rows per wave
+        items, per_block, per_trip = M, ACT_BLOCK * (256 // C), ACT_BLOCK * (256 // C)
+    else:
+        raise KeyError(kernel)
+    wanted = (items + per_block - 1) // per_block
+    return wanted, grid_for(items, per_block, GRID_CAP), items, per_trip
+
+
+CHAIN_KERNELS = ("edge_build", "group_max", "group_sum", "edge_bn_bwd_reduce", "edge_bn_bwd_apply", "gather_sum_rows")
+# (B, N, k, C): the lpdnetorigin step (M = 180 224 points, E = 3 604 480 edge rows) and two wider layers; every kernel of the chain,
+# the edge_bn_bwd reduction included, launches at the cap with a part-filled last trip (B = 5 at C = 256 would not: 2560 blocks)
+CHAIN_SHAPES = {"c64": (44, 4096, 20, 64), "c128": (17, 4096, 20, 128), "c256": (9, 4096, 20, 256)}
+
+
+def vlad_bwd_slices(B, F, KC=64):
+    """slices per cloud of lpd_vlad_finalize_bwd; 0 = the one-block-per-cloud kernel with atomic dcw2"""
+    G = 8
+    while G > 1 and B * G * (1 + 2 * KC) > F * KC:
+        G >>= 1
+    if B * G * (1 + 2 * KC) <= F * KC and F >= 8 * G and B <= 65535:
+        return G
+    return 0
+
+
+# (B, F) -> slices: every regime at F = 1024, and F < 8 G at one cloud
+VLAD_BWD_CASES = {(44, 1024): 8, (66, 1024): 4, (130, 1024): 2, (300, 1024): 1, (520, 1024): 0, (1, 32): 0}
+
+
+def graph_transpose_path(N):
+    """lpd_graph_transpose: one LDS-atomic kernel for N <= 32768, else global-atomic count, scan and fill"""
+    return "lds" if N <= 32768 else "global"
+
+
+# name -> (B, N, k, path)
+GRAPH_CASES = {"global": (2, 40000, 20, "global"), "train": (44, 4096, 20, "lds"), "stress": (2, 16384, 64, "lds")}
+
+
+def dw_smallk_launch(M, Co):
+    """(grid, stride, rows of the four-row unrolled loop per thread are whole: no tail) of lpd_dw_smallk"""
+    rg = 256 // Co
+    grid = grid_for(M, rg * 64, GRID_CAP)
+    step = grid * rg
+    return grid, step, M % (4 * step) == 0
+
+
+DW_SMALLK_ROWS = {"exact": 180_224, "tail": 175_001}

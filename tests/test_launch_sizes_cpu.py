@@ -45,3 +45,51 @@ def test_bnbwd_product_shape_passes_its_cap(mode):
     tpb, cap = ls.BNBWD[mode]
     assert grid == cap and ls.BNBWD_SHAPE["M"] * ls.BNBWD_SHAPE["k"] > 4 * cap * tpb * 32 and ragged
     assert (ls.BNBWD_SHAPE["M"] * ls.BNBWD_SHAPE["k"]) % 32 == 0
+
+
+# ---- tests/test_train_bwd_ops_gpu.py: the training-path kernels of csrc/lpd_train.hip
+def test_grid_for_mirror():
+    assert [ls.grid_for(n, 256) for n in (1, 256, 257, 4096 * 256, 4096 * 256 + 1, 10 ** 9)] == [1, 1, 2, 4096, 4096, 4096]
+    assert ls.chain_launch("group_max", 2 * 4096, 64)[:2] == (512, 512)         # the op tests' largest size (B = 2): one partial trip
+
+
+@pytest.mark.parametrize("name", sorted(ls.CHAIN_SHAPES))
+def test_edge_chain_shapes_pass_the_grid_cap(name):
+    B, N, k, C = ls.CHAIN_SHAPES[name]
+    assert N <= 32768 and C in (64, 128, 256)
+    for kernel in ls.CHAIN_KERNELS:
+        wanted, grid, items, per_trip = ls.chain_launch(kernel, B * N, C)
+        assert grid == ls.GRID_CAP and wanted > ls.GRID_CAP, (kernel, wanted)
+        assert items > 2 * grid * per_trip and items % (grid * per_trip) != 0, (kernel, items / (grid * per_trip))   # > 2 trips, the last part-filled
+    if name == "c64":
+        assert (B, N, k) == (44, 4096, 20)                                          # the lpdnetorigin training step
+    assert ls.chain_launch("edge_bn_bwd_reduce", 5 * 4096, 256)[0] < ls.GRID_CAP   # why C = 256 needs B = 9
+
+
+@pytest.mark.parametrize("B,F", sorted(ls.VLAD_BWD_CASES))
+def test_vlad_finalize_bwd_cases_reach_their_regime(B, F):
+    G = ls.vlad_bwd_slices(B, F)
+    assert G == ls.VLAD_BWD_CASES[(B, F)]
+    if G:
+        assert G == 1 or ls.vlad_bwd_slices(B - 1, F) == G                          # inside the regime, not on its lower edge only
+    else:
+        assert B * 129 > F * 64 or F < 64                                            # the fallback: too many clouds, or F < 8 G
+    assert sorted(set(ls.VLAD_BWD_CASES.values())) == [0, 1, 2, 4, 8]                # every regime has a case
+
+
+@pytest.mark.parametrize("name", sorted(ls.GRAPH_CASES))
+def test_graph_transpose_cases_take_their_path(name):
+    B, N, k, path = ls.GRAPH_CASES[name]
+    assert ls.graph_transpose_path(N) == path and B >= 2                             # B >= 2: a cloud's base offset is exercised
+    assert B * N * k < 2 ** 31
+    assert {p for _, _, _, p in ls.GRAPH_CASES.values()} == {"lds", "global"}
+
+
+@pytest.mark.parametrize("Co", [64, 128, 256])
+def test_dw_smallk_rows_reach_both_loops(Co):
+    grid, step, whole = ls.dw_smallk_launch(ls.DW_SMALLK_ROWS["exact"], Co)
+    assert whole and ls.DW_SMALLK_ROWS["exact"] // step >= 16                       # the unrolled loop only
+    if Co == 64:
+        assert (grid, step) == (704, 2816)
+    grid, step, whole = ls.dw_smallk_launch(ls.DW_SMALLK_ROWS["tail"], Co)
+    assert not whole and ls.DW_SMALLK_ROWS["tail"] // step >= 16                     # the unrolled loop and the tail
