@@ -730,6 +730,12 @@ def apply_transform(x, trans, rows_per_cloud, out=None):
         return out
     if not x.is_contiguous():
         raise ValueError("apply_transform: x must be contiguous for the batched GEMM")
+    if out is not None:      # rows of [M, K] (column slices allowed) as the batched product's [B, N, K] result
+        _rows(out, "out")
+        if out.shape != (M, K):
+            raise ValueError("apply_transform: out has the wrong shape")
+        gemm(x.view(Bn, rows_per_cloud, K), trans, a_kmajor=False, b_kmajor=True, out=out.view(Bn, rows_per_cloud, K))
+        return out
     y = gemm(x.view(Bn, rows_per_cloud, K), trans, a_kmajor=False, b_kmajor=True)
     return y.view(M, K)
 

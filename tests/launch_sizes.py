@@ -6,9 +6,13 @@ Several kernels change what they do with the launch size alone:
   - the reduction kernels that end in fp64 atomics (csrc/lpd_common.h lpd_reduce_grid): at most 768 blocks, a grid-stride loop beyond;
   - the BatchNorm-backward products on the transposed operand loader (csrc/lpd_train3.hip): at most 256 (fp32) / 512 (bf16) blocks;
   - the training-path kernels of csrc/lpd_train.hip (grid_for: at most 4096 blocks, a grid-stride loop beyond), the slice count of
-    lpd_vlad_finalize_bwd, the two paths of lpd_graph_transpose and the loops of lpd_dw_smallk.
+    lpd_vlad_finalize_bwd, the two paths of lpd_graph_transpose and the loops of lpd_dw_smallk;
+  - the forward head, BatchNorm-apply, mining and loss kernels (csrc/lpd_misc.hip, lpd_affine_act of csrc/lpd_train.hip, csrc/lpd_loss.hip):
+    the per-thread constants of affine_act, the chunk count of vlad_asum, the three softmax kernels, the loops of the gating kernel and the
+    LDS sizes of hard_negatives / metric_loss (tests/test_fwd_ops_gpu.py runs them at the shapes of the FWD_* tables).
 tests/test_launch_sizes_cpu.py checks every entry of the tables below against its stated regime, so a change of a heuristic shows which
-cases stop covering what they claim; tests/test_launch_sizes_gpu.py and tests/test_train_bwd_ops_gpu.py run the kernels at these shapes.
+cases stop covering what they claim; tests/test_launch_sizes_gpu.py, tests/test_train_bwd_ops_gpu.py and tests/test_fwd_ops_gpu.py run the
+kernels at these shapes.
 """
 EM_ROUND = 512        # blocks of one resident round of the fused edge-MLP kernels (two per CU)
 EM_TMAX = 16          # most tiles a block walks (LPD_DEBUG=edge-mlp-tiles=n lowers it)
@@ -177,3 +181,112 @@ def dw_smallk_launch(M, Co):
 
 
 DW_SMALLK_ROWS = {"exact": 180_224, "tail": 175_001}
+
+
+# ---- tests/test_fwd_ops_gpu.py: the forward head, BatchNorm apply, mining and loss kernels
+def affine_act_launch(R, C):
+    """(blocks wanted, blocks launched, fixed_q) of lpd_affine_act / lpd_affine_act2: one float4 per thread and trip, four trips per
+    block by design; fixed_q = the grid stride is a multiple of the C / 4 column quads, so a thread loads scale / shift once"""
+    q = C // 4
+    items = R * q
+    wanted = (items + 1023) // 1024
+    grid = grid_for(items, 1024, GRID_CAP)
+    return wanted, grid, (grid * 256) % q == 0
+
+
+# name -> (R, C, capped, fixed_q)
+FWD_AFFINE_SHAPES = {
+    "small": (3000, 64, False, True),
+    "capped_pow2": (20001, 1024, True, True),
+    "capped_reload": (420000, 40, True, False),
+    "reload": (5461, 12, False, False),
+    "c2048_odd_grid": (150, 2048, False, False),
+}
+
+
+def vlad_asum_chunks(N):
+    """blocks per cloud of vlad_asum_kernel (lpd_vlad_finalize without a ready a_sum)"""
+    return 16 if N >= 1024 else (N + 63) // 64
+
+
+# N -> (chunks, rows of the last chunk, blocks that get no row at all)
+def vlad_asum_split(N):
+    g = vlad_asum_chunks(N)
+    chunk = (N + g - 1) // g
+    full = (N + chunk - 1) // chunk          # chunks that own at least one row
+    return g, N - (full - 1) * chunk, g - full
+
+
+FWD_VLAD_N = {63: "per64", 64: "per64", 65: "per64", 1023: "per64", 1024: "chunk16", 1030: "chunk16", 4096: "chunk16"}
+FWD_VLAD_CASES = [(63, 96), (64, 1000), (65, 1024), (1023, 1000), (1024, 96), (1030, 1024), (4096, 1024), (4096, 1000)]     # (N, F), B = 44
+
+
+def softmax_kernel(ncols, group_rows, aligned, parts=None):
+    """which kernel lpd_softmax_affine / lpd_softmax_affine_parts launches; group_rows None = no column sums"""
+    if parts is not None:
+        if parts not in (1, 2, 4, 8) or ncols != 64 or group_rows is None or group_rows % 64 or not aligned:
+            raise ValueError("lpd_softmax_affine_parts refuses")
+        return f"colsum64<{parts}>"
+    if ncols < 1 or ncols > 64:
+        raise ValueError("ncols")
+    if group_rows is None:
+        return "rows"
+    if group_rows % 16:
+        raise ValueError("group_rows % 16")
+    return "colsum64<1>" if (ncols == 64 and group_rows % 64 == 0 and aligned) else "colsum"
+
+
+# (ncols, colsum_rows, aligned) -> kernel
+FWD_SOFTMAX_CASES = {(64, None, True): "rows", (40, None, True): "rows", (1, None, True): "rows",
+                     (64, 4096, True): "colsum64<1>", (64, 4096, False): "colsum", (40, 4096, True): "colsum", (1, 4096, True): "colsum",
+                     (64, 208, True): "colsum"}
+FWD_SOFTMAX_ROWS = (32 * 4096, 44 * 4096)
+
+
+def gating_loops(D):
+    """(column tiles of 256, k per quarter, the 8-unrolled loop leaves a tail in some quarter, trips of the hrow fill) of gating_kernel"""
+    kper = (D + 3) // 4
+    tail = any((min(kq * kper + kper, D) - kq * kper) % 8 for kq in range(4) if kq * kper < D)
+    return (D + 255) // 256, kper, tail, (D + 1023) // 1024
+
+
+# D -> (tiles, kper, tail, fill trips)
+FWD_GATING_D = {256: (1, 64, False, 1), 300: (2, 75, True, 1), 1100: (5, 275, True, 2), 2048: (8, 512, False, 2)}
+FWD_GATING_CASES = [(1, 256), (44, 256), (128, 256), (44, 300), (128, 300), (1, 1100), (44, 1100), (44, 2048)]     # (B, D)
+GATING_DMAX = 8192
+
+
+HARD_NEG_NC_MAX = 36864
+
+
+def hard_negatives_lds_bytes(nc):
+    """dynamic LDS of hard_negatives_kernel (one fp32 distance per candidate); None = refused by the host check"""
+    return 4 * nc if 0 < nc <= HARD_NEG_NC_MAX else None
+
+
+METRIC_LOSS_LDS_MAX = 60 * 1024
+
+
+def metric_loss_lds_bytes(bq, P, Ng):
+    """dynamic LDS of metric_loss_kernel: dpos [bq][P], dneg and d2 [bq][Ng], t1 and t2 [bq], two weights, four reduction slots"""
+    return 4 * (bq * (P + 2 * Ng) + 2 * bq + 2 + 4)
+
+
+# (bq, P, Ng): the largest launch the guard lets through at bq = 8, P = 2, and the first one it refuses
+METRIC_LOSS_FITS = (8, 2, 957)
+METRIC_LOSS_REFUSED = (8, 2, 958)
+
+
+def quad_launch(kernel, M, C):
+    """(blocks wanted, blocks launched) of group_max_bwd (one thread per point and column quad) / scatter_add_rows (one wave per point)"""
+    if kernel == "group_max_bwd":
+        items, per_block = M * (C // 4), 256
+    elif kernel == "scatter_add_rows":
+        items, per_block = M, ACT_BLOCK
+    else:
+        raise KeyError(kernel)
+    return (items + per_block - 1) // per_block, grid_for(items, per_block, GRID_CAP)
+
+
+# (M, C, k) -> capped
+FWD_GROUP_MAX_BWD = {(70001, 64, 20): True, (3000, 256, 7): False}

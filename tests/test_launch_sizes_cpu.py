@@ -93,3 +93,76 @@ def test_dw_smallk_rows_reach_both_loops(Co):
         assert (grid, step) == (704, 2816)
     grid, step, whole = ls.dw_smallk_launch(ls.DW_SMALLK_ROWS["tail"], Co)
     assert not whole and ls.DW_SMALLK_ROWS["tail"] // step >= 16                     # the unrolled loop and the tail
+
+
+# ---- tests/test_fwd_ops_gpu.py: the forward head, BatchNorm apply, mining and loss kernels
+@pytest.mark.parametrize("name", sorted(ls.FWD_AFFINE_SHAPES))
+def test_affine_act_shapes_reach_their_regime(name):
+    R, C, capped, fixed = ls.FWD_AFFINE_SHAPES[name]
+    wanted, grid, fixed_q = ls.affine_act_launch(R, C)
+    assert C % 4 == 0 and (wanted > ls.GRID_CAP) == capped and (grid == ls.GRID_CAP) == capped and fixed_q == fixed, (wanted, grid, fixed_q)
+    if capped:
+        assert (R * (C // 4)) % (grid * 256) != 0                                    # the last grid stride is part-filled
+    if name == "c2048_odd_grid":
+        assert C == 2048 and grid % 2 == 1
+    if name == "reload":
+        assert (C // 4) & (C // 4 - 1)                                               # C / 4 is not a power of two
+
+
+def test_affine_act_launch_mirror():
+    assert ls.affine_act_launch(32 * 4096, 256) == (8192, 4096, True)               # B = 32, N = 4096: C >= 256 walks the grid-stride loop
+    assert ls.affine_act_launch(32 * 4096, 128)[:2] == (4096, 4096) and ls.affine_act_launch(32 * 4096, 64)[0] == 2048
+    # every width of the form 4 * 2^n <= 1024 keeps its column quad; 2048 does with an even grid only
+    assert all(ls.affine_act_launch(R, C)[2] for C in (4, 8, 64, 256, 1024) for R in (1, 77, 5000))
+    assert ls.affine_act_launch(152, 2048)[1:] == (76, True)
+
+
+@pytest.mark.parametrize("N", sorted(ls.FWD_VLAD_N))
+def test_vlad_asum_cases_reach_their_regime(N):
+    g, last, idle = ls.vlad_asum_split(N)
+    assert ("chunk16" if g == 16 and N >= 1024 else "per64") == ls.FWD_VLAD_N[N]
+    assert 0 < last and idle >= 0
+    want = {63: (1, 63, 0), 64: (1, 64, 0), 65: (2, 32, 0), 1023: (16, 63, 0), 1024: (16, 64, 0), 1030: (16, 55, 0), 4096: (16, 256, 0)}
+    assert (g, last, idle) == want[N]
+    assert {N for N, _ in ls.FWD_VLAD_CASES} == set(ls.FWD_VLAD_N) and {F for _, F in ls.FWD_VLAD_CASES} == {96, 1000, 1024}
+    assert any(F % 64 for _, F in ls.FWD_VLAD_CASES)                                  # a short last feature block of the residual pass
+
+
+@pytest.mark.parametrize("case", sorted(ls.FWD_SOFTMAX_CASES, key=str))
+def test_softmax_cases_pick_their_kernel(case):
+    assert ls.softmax_kernel(*case) == ls.FWD_SOFTMAX_CASES[case]
+    assert set(ls.FWD_SOFTMAX_CASES.values()) == {"rows", "colsum", "colsum64<1>"}
+    assert all(r % 4096 == 0 for r in ls.FWD_SOFTMAX_ROWS)
+    assert [ls.softmax_kernel(64, 320, True, parts=p) for p in (1, 2, 4, 8)] == ["colsum64<1>", "colsum64<2>", "colsum64<4>", "colsum64<8>"]
+    with pytest.raises(ValueError):
+        ls.softmax_kernel(64, 320, True, parts=3)
+
+
+@pytest.mark.parametrize("D", sorted(ls.FWD_GATING_D))
+def test_gating_sizes_reach_their_loops(D):
+    assert ls.gating_loops(D) == ls.FWD_GATING_D[D]
+    assert {d for _, d in ls.FWD_GATING_CASES} == set(ls.FWD_GATING_D) and {b for b, _ in ls.FWD_GATING_CASES} == {1, 44, 128}
+    rows = list(ls.FWD_GATING_D.values())
+    assert any(t > 1 for t, _, _, _ in rows) and any(tail for _, _, tail, _ in rows) and any(f > 1 for _, _, _, f in rows)
+    assert any(D % 256 for D in ls.FWD_GATING_D)                                      # a part-filled last column tile
+    assert ls.gating_loops(ls.GATING_DMAX)[3] == 8
+
+
+def test_lds_guards():
+    assert ls.hard_negatives_lds_bytes(4000) == 16000 and ls.hard_negatives_lds_bytes(ls.HARD_NEG_NC_MAX) == 144 * 1024
+    assert ls.hard_negatives_lds_bytes(ls.HARD_NEG_NC_MAX + 1) is None
+    assert ls.hard_negatives_lds_bytes(4000) < 64 * 1024 < ls.hard_negatives_lds_bytes(ls.HARD_NEG_NC_MAX) <= 160 * 1024 - 64   # past the default limit, inside the CU's LDS
+    assert ls.metric_loss_lds_bytes(*ls.METRIC_LOSS_FITS) <= ls.METRIC_LOSS_LDS_MAX < ls.metric_loss_lds_bytes(*ls.METRIC_LOSS_REFUSED)
+    assert ls.METRIC_LOSS_REFUSED[2] == ls.METRIC_LOSS_FITS[2] + 1
+    assert ls.metric_loss_lds_bytes(2, 2, 18) == 4 * (2 * 38 + 4 + 6)
+
+
+@pytest.mark.parametrize("case", sorted(ls.FWD_GROUP_MAX_BWD))
+def test_group_max_bwd_cases_sit_on_both_sides_of_the_cap(case):
+    M, C, k = case
+    wanted, grid = ls.quad_launch("group_max_bwd", M, C)
+    assert (wanted > ls.GRID_CAP) == ls.FWD_GROUP_MAX_BWD[case] and grid == min(wanted, ls.GRID_CAP)
+    if wanted > ls.GRID_CAP:
+        assert (M * (C // 4)) % (grid * 256) != 0
+    assert sorted(ls.FWD_GROUP_MAX_BWD.values()) == [False, True]
+    assert ls.quad_launch("scatter_add_rows", 20000, 64) == (5000, 4096)             # the size a scatter_add_rows case would need
