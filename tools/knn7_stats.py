@@ -19,8 +19,8 @@ for name, feat in (("xyz", ops.transpose(xs.view(B, N, 3))), ("feat64", None)):
         w = st.view(-1, 32, 5)[:, 0, :]     # per wave (first query of each tile)
         if k >= 12:
             ph = raw.view(-1, 32, k)[:, 0, 5:12].float()
-            print(name, "low-precision tests/wave %.1f; cycles/wave: advance %.0f  exact tile %.0f  select+queue %.0f  drain %.0f  total %.0f; bound tests %.1f" % tuple(ph.mean(0).tolist()), flush=True)
-        print(name, label, "tiles visited/wave %.1f  drain iterations %.1f  drains %.1f  admitted per half-lane %.1f / %.1f" % (
+            print(name, "drain batches/wave %.1f; cycles/wave: advance %.0f  exact tile %.0f  select+queue %.0f  drain %.0f  total %.0f; bound tests %.1f" % tuple(ph.mean(0).tolist()), flush=True)
+        print(name, label, "tiles visited/wave %.1f  sum of the drains' fullest lanes %.1f  drains %.1f  admitted per half-lane %.1f / %.1f" % (
             w[:, 0].mean(), w[:, 1].mean(), w[:, 3].mean(), st[:, 2].mean(), st[:, 4].mean()), flush=True)
     for impl in (4, 6):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
