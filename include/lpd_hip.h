@@ -307,19 +307,22 @@ int lpd_transpose(const float* in, float* out, int batch, int R, int C, int ldi,
 /* NetVLAD soft-assignment: out[r][:] = softmax(scale * in[r][:] + shift), ncols <= 64
  * (util/PointNetVlad.py:51-58, eval-mode bn1 folded into scale/shift). In-place allowed.
  * colsum != NULL: rows come in groups (clouds) of group_rows (a multiple of 16) and colsum[g * colsum_ld + c] receives
- * (+=, float atomics; the caller zeroes it) the column sums of `out` over group g -- NetVLAD's a_sum (:63) without a
- * second pass over the assignments. */
+ * (=) the column sums of `out` over group g -- NetVLAD's a_sum (:63) without a second pass over the assignments; the other
+ * colsum_ld - ncols entries of row g are set to 0.  part: scratch of rows / 16 * 64 floats for the partial sums, which a
+ * second launch adds in a fixed order (no float atomics: the same input gives the same bits in every launch). */
 int lpd_softmax_affine(const float* in, float* out, int rows, int ncols, const float* scale, const float* shift,
-                       int group_rows, float* colsum, int colsum_ld, void* stream);
+                       int group_rows, float* colsum, int colsum_ld, float* part, void* stream);
 
 /* NetVLAD residual + normalisations (util/PointNetVlad.py:61-74).
  *   vraw [B][F][KC] = act^T x per cloud, act [B][N][KC], cw2 [F][KC] (cluster_weights2[0]),
  *   out [B][F*KC]: (vraw - a_sum*cw2), L2-normalised over F per cluster, flattened f*KC+c, L2-normalised. KC = 64.
- *   ws: workspace of B*2*KC floats (a_sum and per-cluster sums of squares, zeroed here); asum_ready != 0: ws[b][0..KC)
- *   already holds a_sum (lpd_softmax_affine with colsum = ws, colsum_ld = 2*KC), ws[b][KC..2KC) is zero, act may be NULL.
+ *   ws: workspace of B*2*KC floats, ws[b][0..KC) = a_sum (written here); asum_ready != 0: ws[b][0..KC) already holds a_sum
+ *   (lpd_softmax_affine with colsum = ws, colsum_ld = 2*KC), act may be NULL.  ws[b][KC..2KC) is not touched.
+ *   part: scratch of B*(16 + ceil(F/64))*KC floats: per-block partial sums of a_sum and of the per-cluster sums of squares,
+ *   added by their readers in block order (no float atomics: the same input gives the same bits in every launch).
  *   aux_asum [B][KC], aux_inv_c [B][KC], aux_inv_g [B]: optional (NULL in inference) -- a_sum and the two
  *   reciprocal norms, saved for lpd_vlad_finalize_bwd. */
-int lpd_vlad_finalize(const float* vraw, const float* act, const float* cw2, float* out, float* ws, float* aux_asum,
+int lpd_vlad_finalize(const float* vraw, const float* act, const float* cw2, float* out, float* ws, float* part, float* aux_asum,
                       float* aux_inv_c, float* aux_inv_g, int B, int N, int F, int KC, int asum_ready, void* stream);
 
 /* Per-cloud max over the N points: in [B][N][ldi] -> out [B][C]
@@ -404,6 +407,34 @@ int lpd_f64_to_f32(const double* in, float* out, long long n, void* stream);
  * invariant to point order; sorting makes the neighbour gathers of the aggregation kernels cache-local.
  * xyz/out [B][N][3] (out != xyz), perm [B][N] int32 or NULL.  N <= 16384. */
 int lpd_morton_sort(const float* xyz, float* out, int32_t* perm, int B, int N, void* stream);
+
+/*
+ * Local point-distribution features from sorted neighbour lists (csrc/lpd_feat.hip): the handcrafted per-point columns that the
+ * use_mFea trunks take behind xyz (reference lpdnet_model.py:183-186,215-224; the reference reads them from an offline step).
+ *   xyz   [B*N][ldx] point-major, three coordinates used
+ *   idx   [B][N][K] int32, local to the cloud, nearest first (lpd_knn_pm's output; any list is legal -- an index outside the cloud
+ *         is read as the cloud's last point)
+ *   cand  HOST array of ncand <= 16 strictly ascending neighbourhood sizes, 4 <= cand[i] <= K, read at call time and handed to the
+ *         kernel by value; NULL / ncand == 0: one fixed size k = K.  With candidates the size with the smallest eigenentropy is
+ *         used (ties: the smaller size) and ALL columns are taken at that size; the list is walked once, not once per candidate.
+ *   sel   bit mask over the ten columns below; the selected ones are written in ascending column order to
+ *         out[m*ldo + (copy_xyz ? 3 : 0) + j]; copy_xyz = 1 also writes the point's coordinates to the first three entries of the row
+ *         (five columns, ldo = 8: the [B*N, 8] input rows of a use_mFea trunk from one launch).  Entries of a row behind the
+ *         written ones are left untouched.
+ *   kopt  [B*N] int32 or NULL: the neighbourhood size used for each point
+ * For point i, list n_0 .. n_{K-1} and size k, with d_j = x_{n_j} - x_i over the first k entries (moments are accumulated on d_j,
+ * centred on the query point): mu = mean d_j, S = mean d_j d_j^T - mu mu^T, l1 >= l2 >= l3 the eigenvalues of S clamped at 0
+ * (six cyclic Jacobi sweeps in fp32), n the unit eigenvector of l3, s = l1 + l2 + l3, e_i = l_i / s.
+ *   0 change of curvature e3         1 omnivariance cbrt(e1 e2 e3)       2 linearity (l1 - l2) / l1
+ *   3 eigenentropy -sum e_i ln e_i   4 verticality |n_z|                 5 2-D scattering S_xx + S_yy
+ *   6 2-D linearity: smaller / larger eigenvalue of the xy block of S    7 height range max d_j.z - min d_j.z
+ *   8 height variance S_zz           9 density k / ((4/3) pi r^3), r = |d_{k-1}|
+ * s == 0: columns 0-4 are 0; l1 == 0: 2 is 0; larger 2-D eigenvalue 0: 6 is 0; r == 0: 9 is 0.
+ * Supported: 4 <= K <= 64, K <= N.  Clouds of N <= 4096 points are staged in LDS, larger ones read their neighbours through L2:
+ * same bits either way.
+ */
+int lpd_local_features(const float* xyz, int ldx, const int32_t* idx, int B, int N, int K, const int32_t* cand, int ncand, unsigned sel,
+                       int copy_xyz, float* out, int ldo, int32_t* kopt, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
@@ -704,9 +735,9 @@ int lpd_gemm_p8_fused(const void* a_hi, const void* a_lo, long long a_cloud, int
                       long long c_cloud, int c_panel_ld, int M, int N, int K, int panel_n, const float* bias, int act, float slope,
                       const void* w2_frags, float* parts, long long part_stride, void* stream);
 /* softmax(scale * (sum of `parts` planes of in, part_stride floats apart) + shift) over 64 columns, with the per-group column sums
- * of lpd_softmax_affine (group_rows % 64 == 0); parts in {1, 2, 4, 8} */
+ * of lpd_softmax_affine (group_rows % 64 == 0; part: its scratch, rows floats are used); parts in {1, 2, 4, 8} */
 int lpd_softmax_affine_parts(const float* in, int parts, long long part_stride, float* out, int rows, const float* scale,
-                             const float* shift, int group_rows, float* colsum, int colsum_ld, void* stream);
+                             const float* shift, int group_rows, float* colsum, int colsum_ld, float* part, void* stream);
 /* fp32 cloud panels [clouds][panels][s_panel_ld][8] (s_cloud floats apart) -> the two bf16 planes hi / lo of the same layout
  * ([clouds][panels][d_panel_ld][8], d_cloud elements apart); n rows per panel are converted. */
 int lpd_split_panels(const float* src, long long s_cloud, int s_panel_ld, void* hi, void* lo, long long d_cloud, int d_panel_ld,

@@ -78,16 +78,18 @@ __global__ void softmax_affine_kernel(const float* __restrict__ in, float* __res
 }
 
 // The same with the per-cloud column sums of the result (NetVLAD's a_sum, util/PointNetVlad.py:63) accumulated on the way:
-// one wavefront walks SM_RPW consecutive rows of one cloud (lane = column), four rows in flight, and adds its 64 partial
-// sums to colsum[cloud][lane] with one atomic instruction -- the separate a_sum pass re-read the 33 MB of assignments
-// (28 us at B = 32; this kernel: the softmax's own time).
+// one wavefront walks SM_RPW consecutive rows of one cloud (lane = column), four rows in flight, and stores its 64 partial
+// sums to part[wave][lane]; colsum_reduce_kernel adds a cloud's partials in a FIXED order -- the separate a_sum pass re-read the
+// 33 MB of assignments (28 us at B = 32; this kernel: the softmax's own time).  No float atomics: their order varies from launch
+// to launch, and with it the last bits of every descriptor; two forwards of one input are bit-equal.
 constexpr int SM_RPW = 16;
 __global__ __launch_bounds__(256) void softmax_affine_colsum_kernel(const float* __restrict__ in, float* __restrict__ out, int rows,
                                                                     int ncols, const float* scale, const float* shift,
-                                                                    int group_rows, float* __restrict__ colsum, int colsum_ld)
+                                                                    float* __restrict__ part)
 {
     const int lane = threadIdx.x & 63;
-    const long long row0 = ((long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * SM_RPW;
+    const long long wave = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long row0 = wave * SM_RPW;
     if (row0 >= rows) return;
     const bool on = lane < ncols;
     float sc = 1.0f, sh = 0.0f;
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void softmax_affine_colsum_kernel(const float*
         if (on) out[row * ncols + lane] = p;
         acc += p;
     }
-    if (on) atomicAdd(&colsum[(row0 / group_rows) * colsum_ld + lane], acc);
+    part[wave * 64 + lane] = acc;      // 0 in the columns past ncols
 }
 
 // 64 columns: sixteen lanes per row (float4 each), four rows per wave-instruction -- 1 KiB loads / stores and four
@@ -117,8 +119,8 @@ __global__ __launch_bounds__(256) void softmax_affine_colsum_kernel(const float*
 // lpd_gemm_p8_fused)
 template <int PARTS = 1>
 __global__ __launch_bounds__(256) void softmax_affine_colsum64_kernel(const float* __restrict__ in, float* __restrict__ out, int rows,
-                                                                      const float* scale, const float* shift, int group_rows,
-                                                                      float* __restrict__ colsum, int colsum_ld, long long part_stride = 0)
+                                                                      const float* scale, const float* shift,
+                                                                      float* __restrict__ part, long long part_stride = 0)
 {
     const int lane = threadIdx.x & 63;
     const int q = lane & 15, sub = lane >> 4;                  // column quad, row inside the group of four
@@ -152,15 +154,30 @@ __global__ __launch_bounds__(256) void softmax_affine_colsum64_kernel(const floa
         acc.x += __shfl_xor(acc.x, o, 64); acc.y += __shfl_xor(acc.y, o, 64);
         acc.z += __shfl_xor(acc.z, o, 64); acc.w += __shfl_xor(acc.w, o, 64);
     }
-    // one 256-byte atomic instruction per workgroup (its 4 x SM_RPW rows lie in one cloud): every wave of a cloud adds
-    // into the same 64 floats, and the first version's four 16-lane atomics per WAVE cost more than the softmax itself
-    __shared__ float part[4][64];
-    if (sub == 0) *reinterpret_cast<float4*>(&part[threadIdx.x >> 6][4 * q]) = acc;
+    // one 256-byte store per workgroup (its 4 x SM_RPW rows lie in one cloud)
+    __shared__ float wsum[4][64];
+    if (sub == 0) *reinterpret_cast<float4*>(&wsum[threadIdx.x >> 6][4 * q]) = acc;
     __syncthreads();
-    if (threadIdx.x < 64) {
-        const float t = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-        atomicAdd(colsum + (row0 / group_rows) * colsum_ld + lane, t);
-    }
+    if (threadIdx.x < 64)
+        part[(long long)blockIdx.x * 64 + lane] = (wsum[0][lane] + wsum[1][lane]) + (wsum[2][lane] + wsum[3][lane]);
+}
+
+// colsum[cloud][0..ncols) = the sum of the cloud's `per` consecutive partial rows (64 floats each) in a fixed order: four strided
+// running sums, then (0 + 1) + (2 + 3); the other colsum_ld - ncols entries of the row are zeroed (the caller's workspace row is
+// wider than the sums).  grid = clouds.
+__global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restrict__ part, int per, int ncols,
+                                                            float* __restrict__ colsum, int colsum_ld)
+{
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const float* p = part + (long long)blockIdx.x * per * 64 + lane;
+    float s = 0.0f;
+    for (int j = g; j < per; j += 4) s += p[(long long)j * 64];
+    red[g][lane] = s;
+    __syncthreads();
+    float* o = colsum + (long long)blockIdx.x * colsum_ld;
+    if (threadIdx.x < 64 && lane < ncols) o[lane] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    for (int c = ncols + threadIdx.x; c < colsum_ld; c += 256) o[c] = 0.0f;
 }
 
 // block reduce helper (sum) over 256 threads
@@ -175,13 +192,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* red)
 }
 
 // NetVLAD finalize in three multi-block passes (grid y = cloud), vraw [B][F][KC] (index f*KC + c), act [B][N][KC]:
-//   1. a_sum[b][c] = sum_n act[b][n][c]                         (atomics into ws[b][0..KC))
-//   2. r = vraw - a_sum * cw2 -> out ; column sums of squares    (atomics into ws[b][KC..2KC))
+//   1. a_sum[b][c] = sum_n act[b][n][c]                         (one partial per block into pa[b][chunk][KC])
+//   2. r = vraw - a_sum * cw2 -> out ; column sums of squares    (one partial per block into ps[b][fblock][KC])
+// The partials are added by their readers in block order -- no float atomics, the result does not vary between launches.
 //   3. out *= inv_c[c] * inv_g, inv_c = 1/max(|r[:,c]|, eps), inv_g = 1/max(sqrt(sum_c |r[:,c]|^2 inv_c^2), eps)
 // (after the intra-normalisation every non-degenerate column has unit norm, so the global norm follows from the
 //  column norms alone -- no third reduction over the 65536 values).
 template <int KC>
-__global__ __launch_bounds__(256) void vlad_asum_kernel(const float* __restrict__ act, float* __restrict__ ws, int N)
+__global__ __launch_bounds__(256) void vlad_asum_kernel(const float* __restrict__ act, float* __restrict__ pa, int N)
 {
     __shared__ float part[256];
     constexpr int RPB = 256 / KC;
@@ -197,13 +215,14 @@ __global__ __launch_bounds__(256) void vlad_asum_kernel(const float* __restrict_
     if (tid < KC) {
         float t = 0.0f;
         for (int r = 0; r < RPB; ++r) t += part[r * KC + tid];
-        atomicAdd(&ws[(size_t)b * 2 * KC + tid], t);
+        pa[((size_t)b * gridDim.x + blockIdx.x) * KC + tid] = t;
     }
 }
 
 template <int KC>
 __global__ __launch_bounds__(256) void vlad_resid_kernel(const float* __restrict__ vraw, const float* __restrict__ cw2,
-                                                         float* __restrict__ out, float* __restrict__ ws, int F, int FCH)
+                                                         float* __restrict__ out, float* __restrict__ ws,
+                                                         const float* __restrict__ pa, int nchunks, float* __restrict__ ps, int F, int FCH)
 {
     __shared__ float part[256];
     constexpr int RPB = 256 / KC;
@@ -212,7 +231,14 @@ __global__ __launch_bounds__(256) void vlad_resid_kernel(const float* __restrict
     const int f0 = blockIdx.x * FCH, f1 = min(f0 + FCH, F);
     const float* v = vraw + (size_t)b * F * KC;
     float* o = out + (size_t)b * F * KC;
-    const float as = ws[(size_t)b * 2 * KC + c];
+    float as;
+    if (nchunks) {       // a_sum from vlad_asum_kernel's partials; block 0 leaves it in ws[b][0..KC) (no block reads it from there)
+        as = 0.0f;
+        for (int j = 0; j < nchunks; ++j) as += pa[((size_t)b * nchunks + j) * KC + c];
+        if (blockIdx.x == 0 && tid < KC) ws[(size_t)b * 2 * KC + c] = as;
+    } else {
+        as = ws[(size_t)b * 2 * KC + c];
+    }
     float ss = 0.0f;
     for (int f = f0 + rg; f < f1; f += RPB) {
         float r = v[(size_t)f * KC + c] - as * cw2[(size_t)f * KC + c];
@@ -224,22 +250,27 @@ __global__ __launch_bounds__(256) void vlad_resid_kernel(const float* __restrict
     if (tid < KC) {
         float t = 0.0f;
         for (int r = 0; r < RPB; ++r) t += part[r * KC + tid];
-        atomicAdd(&ws[(size_t)b * 2 * KC + KC + tid], t);
+        ps[((size_t)b * gridDim.x + blockIdx.x) * KC + tid] = t;
     }
 }
 
 template <int KC>
 __global__ __launch_bounds__(256) void vlad_scale_kernel(float* __restrict__ out, const float* __restrict__ ws,
-                                                         float* aux_asum, float* aux_inv_c, float* aux_inv_g, int F, int FCH)
+                                                         const float* __restrict__ ps, float* aux_asum, float* aux_inv_c,
+                                                         float* aux_inv_g, int F, int FCH)
 {
     __shared__ float s_inv[KC];
+    __shared__ float s_ss[KC];
     __shared__ float s_g;
     constexpr int RPB = 256 / KC;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int c = tid % KC, rg = tid / KC;
     if (tid < KC) {
-        const float inv = 1.0f / fmaxf(sqrtf(ws[(size_t)b * 2 * KC + KC + tid]), 1e-12f);   // F.normalize eps
+        float ss = 0.0f;      // the column's sum of squares: vlad_resid_kernel's partials in block order
+        for (int j = 0; j < (int)gridDim.x; ++j) ss += ps[((size_t)b * gridDim.x + j) * KC + tid];
+        const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);   // F.normalize eps
         s_inv[tid] = inv;
+        s_ss[tid] = ss;
         if (blockIdx.x == 0) {
             if (aux_inv_c) aux_inv_c[b * KC + tid] = inv;
             if (aux_asum) aux_asum[b * KC + tid] = ws[(size_t)b * 2 * KC + tid];
@@ -248,7 +279,7 @@ __global__ __launch_bounds__(256) void vlad_scale_kernel(float* __restrict__ out
     __syncthreads();
     if (tid == 0) {
         float tot = 0.0f;
-        for (int k = 0; k < KC; ++k) tot += ws[(size_t)b * 2 * KC + KC + k] * s_inv[k] * s_inv[k];
+        for (int k = 0; k < KC; ++k) tot += s_ss[k] * s_inv[k] * s_inv[k];
         s_g = 1.0f / fmaxf(sqrtf(tot), 1e-12f);
         if (aux_inv_g && blockIdx.x == 0) aux_inv_g[b] = s_g;
     }
@@ -434,22 +465,26 @@ extern "C" int lpd_transpose(const float* in, float* out, int batch, int R, int 
 }
 
 extern "C" int lpd_softmax_affine(const float* in, float* out, int rows, int ncols, const float* scale, const float* shift,
-                                  int group_rows, float* colsum, int colsum_ld, void* stream_)
+                                  int group_rows, float* colsum, int colsum_ld, float* part, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    LPD_CHECK_ARG(in && out, "lpd_softmax_affine: null pointer");
+    LPD_CHECK_ARG(in && out && (!colsum || part), "lpd_softmax_affine: null pointer");
     LPD_CHECK_ARG(rows > 0 && ncols > 0 && ncols <= 64, "lpd_softmax_affine: bad dims rows=%d ncols=%d (<= 64)", rows, ncols);
     LPD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "lpd_softmax_affine: scale and shift must be given together");
     if (colsum) {
         LPD_CHECK_ARG(group_rows > 0 && group_rows % SM_RPW == 0 && rows % group_rows == 0 && colsum_ld >= ncols,
                       "lpd_softmax_affine: column sums need group_rows %% %d == 0 and rows %% group_rows == 0", SM_RPW);
         const int waves = rows / SM_RPW;
-        if (ncols == 64 && group_rows % (4 * SM_RPW) == 0 && ((((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0))
-            hipLaunchKernelGGL(softmax_affine_colsum64_kernel<1>, dim3((waves + 3) / 4), dim3(256), 0, stream, in, out, rows, scale, shift,
-                               group_rows, colsum, colsum_ld, 0);
-        else
-            hipLaunchKernelGGL(softmax_affine_colsum_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, in, out, rows, ncols, scale, shift,
-                               group_rows, colsum, colsum_ld);
+        int per;
+        if (ncols == 64 && group_rows % (4 * SM_RPW) == 0 && ((((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0)) {      // one partial per workgroup of 4 x SM_RPW rows
+            hipLaunchKernelGGL(softmax_affine_colsum64_kernel<1>, dim3(waves / 4), dim3(256), 0, stream, in, out, rows, scale, shift, part, 0);
+            per = group_rows / (4 * SM_RPW);
+        } else {      // one partial per wave of SM_RPW rows
+            hipLaunchKernelGGL(softmax_affine_colsum_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, in, out, rows, ncols, scale, shift, part);
+            per = group_rows / SM_RPW;
+        }
+        LPD_CHECK_LAUNCH("lpd_softmax_affine");
+        hipLaunchKernelGGL(colsum_reduce_kernel, dim3(rows / group_rows), dim3(256), 0, stream, (const float*)part, per, ncols, colsum, colsum_ld);
     } else {
         hipLaunchKernelGGL(softmax_affine_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, in, out, rows, ncols, scale, shift);
     }
@@ -460,10 +495,10 @@ extern "C" int lpd_softmax_affine(const float* in, float* out, int rows, int nco
 // softmax(scale * (sum of `parts` planes) + shift) over 64 columns + per-group column sums: the consumer of lpd_gemm_p8_fused's
 // partial assignment products.  rows % group_rows == 0, group_rows % 64 == 0.
 extern "C" int lpd_softmax_affine_parts(const float* in, int parts, long long part_stride, float* out, int rows, const float* scale,
-                                        const float* shift, int group_rows, float* colsum, int colsum_ld, void* stream_)
+                                        const float* shift, int group_rows, float* colsum, int colsum_ld, float* part, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    LPD_CHECK_ARG(in && out && colsum, "lpd_softmax_affine_parts: null pointer");
+    LPD_CHECK_ARG(in && out && colsum && part, "lpd_softmax_affine_parts: null pointer");
     LPD_CHECK_ARG((parts == 1 || parts == 2 || parts == 4 || parts == 8) && part_stride >= (long long)rows * 64 && part_stride % 4 == 0,
                   "lpd_softmax_affine_parts: parts in {1, 2, 4, 8}");
     LPD_CHECK_ARG((scale == nullptr) == (shift == nullptr), "lpd_softmax_affine_parts: scale and shift must be given together");
@@ -471,36 +506,43 @@ extern "C" int lpd_softmax_affine_parts(const float* in, int parts, long long pa
                   "lpd_softmax_affine_parts: rows %% group_rows == 0, group_rows %% %d == 0", 4 * SM_RPW);
     LPD_CHECK_ARG((((uintptr_t)in | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0, "lpd_softmax_affine_parts: alignment");
     const int waves = rows / SM_RPW;
-    const dim3 grid((waves + 3) / 4), block(256);
+    const dim3 grid(waves / 4), block(256);
     switch (parts) {
-        case 1: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<1>, grid, block, 0, stream, in, out, rows, scale, shift, group_rows, colsum, colsum_ld, part_stride); break;
-        case 2: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<2>, grid, block, 0, stream, in, out, rows, scale, shift, group_rows, colsum, colsum_ld, part_stride); break;
-        case 4: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<4>, grid, block, 0, stream, in, out, rows, scale, shift, group_rows, colsum, colsum_ld, part_stride); break;
-        default: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<8>, grid, block, 0, stream, in, out, rows, scale, shift, group_rows, colsum, colsum_ld, part_stride); break;
+        case 1: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<1>, grid, block, 0, stream, in, out, rows, scale, shift, part, part_stride); break;
+        case 2: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<2>, grid, block, 0, stream, in, out, rows, scale, shift, part, part_stride); break;
+        case 4: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<4>, grid, block, 0, stream, in, out, rows, scale, shift, part, part_stride); break;
+        default: hipLaunchKernelGGL(softmax_affine_colsum64_kernel<8>, grid, block, 0, stream, in, out, rows, scale, shift, part, part_stride); break;
     }
     LPD_CHECK_LAUNCH("lpd_softmax_affine_parts");
+    hipLaunchKernelGGL(colsum_reduce_kernel, dim3(rows / group_rows), block, 0, stream, (const float*)part, group_rows / (4 * SM_RPW), 64,
+                       colsum, colsum_ld);
+    LPD_CHECK_LAUNCH("lpd_softmax_affine_parts(colsum)");
     return LPD_OK;
 }
 
-extern "C" int lpd_vlad_finalize(const float* vraw, const float* act, const float* cw2, float* out, float* ws,
+extern "C" int lpd_vlad_finalize(const float* vraw, const float* act, const float* cw2, float* out, float* ws, float* part,
                                  float* aux_asum, float* aux_inv_c, float* aux_inv_g, int B, int N, int F, int KC,
                                  int asum_ready, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    LPD_CHECK_ARG(vraw && (act || asum_ready) && cw2 && out && ws, "lpd_vlad_finalize: null pointer");
+    LPD_CHECK_ARG(vraw && (act || asum_ready) && cw2 && out && ws && part, "lpd_vlad_finalize: null pointer");
     LPD_CHECK_ARG(B > 0 && B <= 65535 && N > 0 && F > 0, "lpd_vlad_finalize: bad dims");
     LPD_CHECK_ARG(KC == 64, "lpd_vlad_finalize: cluster_size=%d unsupported (64)", KC);
-    if (!asum_ready) {   // else ws[b][0..KC) already holds a_sum (lpd_softmax_affine with colsum) and ws[b][KC..2KC) is zero
-        (void)hipMemsetAsync(ws, 0, sizeof(float) * (size_t)B * 2 * KC, stream);
-        const int nchunks = N >= 1024 ? 16 : (N + 63) / 64;
-        hipLaunchKernelGGL(vlad_asum_kernel<64>, dim3(nchunks, B), dim3(256), 0, stream, act, ws, N);
+    // part: [B][16][KC] a_sum partials, then [B][fblocks][KC] partial sums of squares
+    float* pa = part;
+    float* ps = part + (size_t)B * 16 * KC;
+    int nchunks = 0;
+    if (!asum_ready) {   // else ws[b][0..KC) already holds a_sum (lpd_softmax_affine with colsum)
+        nchunks = N >= 1024 ? 16 : (N + 63) / 64;
+        hipLaunchKernelGGL(vlad_asum_kernel<64>, dim3(nchunks, B), dim3(256), 0, stream, act, pa, N);
         LPD_CHECK_LAUNCH("lpd_vlad_finalize(asum)");
     }
     const int FCH = 64;
     const int fblocks = (F + FCH - 1) / FCH;
-    hipLaunchKernelGGL(vlad_resid_kernel<64>, dim3(fblocks, B), dim3(256), 0, stream, vraw, cw2, out, ws, F, FCH);
+    hipLaunchKernelGGL(vlad_resid_kernel<64>, dim3(fblocks, B), dim3(256), 0, stream, vraw, cw2, out, ws, (const float*)pa, nchunks, ps, F,
+                       FCH);
     LPD_CHECK_LAUNCH("lpd_vlad_finalize(resid)");
-    hipLaunchKernelGGL(vlad_scale_kernel<64>, dim3(fblocks, B), dim3(256), 0, stream, out, (const float*)ws, aux_asum,
+    hipLaunchKernelGGL(vlad_scale_kernel<64>, dim3(fblocks, B), dim3(256), 0, stream, out, (const float*)ws, (const float*)ps, aux_asum,
                        aux_inv_c, aux_inv_g, F, FCH);
     LPD_CHECK_LAUNCH("lpd_vlad_finalize(scale)");
     return LPD_OK;

@@ -966,13 +966,14 @@ def softmax_affine(x, scale=None, shift=None, out=None, colsum_rows=None):
     scale, shift = _vec(scale, "scale", n), _vec(shift, "shift", n)
     lib = _lib.load()
     if colsum_rows is None:
-        _call("softmax_affine", lib.lpd_softmax_affine, _ptr(x), _ptr(out), rows, n, _ptr(scale), _ptr(shift), 0, None, 0, _stream())
+        _call("softmax_affine", lib.lpd_softmax_affine, _ptr(x), _ptr(out), rows, n, _ptr(scale), _ptr(shift), 0, None, 0, None, _stream())
         return out
     if colsum_rows % 16 or rows % colsum_rows:
         raise ValueError("softmax_affine: colsum_rows must be a multiple of 16 that divides the row count")
-    ws = _zeros((rows // colsum_rows, 2 * n), torch.float32, x.device)
+    ws = torch.empty((rows // colsum_rows, 2 * n), dtype=torch.float32, device=x.device)      # the kernel writes every entry
+    part = torch.empty((rows // 16, 64), dtype=torch.float32, device=x.device)
     _call("softmax_affine", lib.lpd_softmax_affine, _ptr(x), _ptr(out), rows, n, _ptr(scale), _ptr(shift), colsum_rows, _ptr(ws), 2 * n,
-          _stream())
+          _ptr(part), _stream())
     return out, ws
 
 
@@ -987,10 +988,11 @@ def softmax_affine_parts(parts, scale=None, shift=None, colsum_rows=None):
         raise ValueError("softmax_affine_parts: colsum_rows must be a multiple of 64 that divides the row count")
     out = torch.empty((rows, n), dtype=torch.float32, device=parts.device)
     scale, shift = _vec(scale, "scale", n), _vec(shift, "shift", n)
-    ws = _zeros((rows // colsum_rows, 2 * n), torch.float32, parts.device)
+    ws = torch.empty((rows // colsum_rows, 2 * n), dtype=torch.float32, device=parts.device)      # the kernel writes every entry
+    part = torch.empty((rows // 64, 64), dtype=torch.float32, device=parts.device)
     lib = _lib.load()
     _call("softmax_affine", lib.lpd_softmax_affine_parts, _ptr(parts), P, parts.stride(0), _ptr(out), rows, _ptr(scale), _ptr(shift),
-          colsum_rows, _ptr(ws), 2 * n, _stream())
+          colsum_rows, _ptr(ws), 2 * n, _ptr(part), _stream())
     return out, ws
 
 
@@ -1018,8 +1020,9 @@ def vlad_finalize(vraw, act, cw2, out=None, aux=None, ws=None):
             raise ValueError("vlad_finalize: ws must be the [B, 2*KC] workspace of softmax_affine(colsum_rows=N)")
     else:
         ws = torch.empty((B, 2 * KC), dtype=torch.float32, device=vraw.device)
+    part = torch.empty((B, 16 + (F + 63) // 64, KC), dtype=torch.float32, device=vraw.device)
     lib = _lib.load()
-    _call("vlad_finalize", lib.lpd_vlad_finalize, _ptr(vraw), _ptr(act), _ptr(cw2), _ptr(out), _ptr(ws), _ptr(a1), _ptr(a2),
+    _call("vlad_finalize", lib.lpd_vlad_finalize, _ptr(vraw), _ptr(act), _ptr(cw2), _ptr(out), _ptr(ws), _ptr(part), _ptr(a1), _ptr(a2),
           _ptr(a3), B, N, F, KC, int(ready), _stream())
     return out
 
@@ -1070,6 +1073,45 @@ def morton_sort(x, want_perm=False):
     _call("morton_sort", lib.lpd_morton_sort, _ptr(x3), _ptr(out), _ptr(perm), B, N, _stream())
     out = out.view(shape)
     return (out, perm) if want_perm else out
+
+
+def local_features(xyz_rows, idx, B, N, *, candidates=None, columns=range(10), copy_xyz=False, want_k=False, out=None):
+    """Local point-distribution features (lpd_local_features): xyz_rows [B*N, >=3] point-major, idx [B,N,K] int32 sorted nearest-first
+    (knn_pm) -> [B*N, (3 if copy_xyz) + len(columns)] rows, the selected columns in ascending order behind the optional xyz copy.
+    candidates: ascending neighbourhood sizes <= K, the one with the smallest eigenentropy is used per point (None: k = K);
+    want_k: also return the size used, [B*N] int32.  out: rows to write into (may be wider than the result: the rest is untouched)."""
+    _req(xyz_rows, "xyz_rows")
+    _req(idx, "idx", torch.int32)
+    ldx = _rows(xyz_rows, "xyz_rows")
+    if xyz_rows.shape[0] != B * N or xyz_rows.shape[1] < 3:
+        raise ValueError("local_features: xyz_rows must be [B*N, >=3]")
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
+        raise ValueError(f"local_features: idx must be [B,N,K], got {tuple(idx.shape)}")
+    idx = idx.contiguous()
+    K = idx.shape[2]
+    sel = 0
+    for c in columns:
+        if not 0 <= int(c) < 10 or sel >> int(c) & 1:
+            raise ValueError(f"local_features: columns must be distinct and in 0..9, got {list(columns)}")
+        sel |= 1 << int(c)
+    if list(columns) != sorted(columns):
+        raise ValueError("local_features: columns are written in ascending order; pass them sorted")
+    width = (3 if copy_xyz else 0) + bin(sel).count("1")
+    if out is None:
+        out = torch.empty((B * N, width), dtype=torch.float32, device=xyz_rows.device)
+    ldo = _rows(out, "out")
+    if out.shape[0] != B * N:
+        raise ValueError("local_features: out must have B*N rows")
+    cand = None
+    ncand = 0
+    if candidates is not None:
+        ncand = len(candidates)
+        cand = (ctypes.c_int32 * max(1, ncand))(*[int(c) for c in candidates])      # host array, read by the call
+    kopt = torch.empty((B * N,), dtype=torch.int32, device=xyz_rows.device) if want_k else None
+    lib = _lib.load()
+    _call(f"local_features[k={K}]", lib.lpd_local_features, _ptr(xyz_rows), ldx, _ptr(idx), B, N, K, cand, ncand, sel, int(bool(copy_xyz)),
+          _ptr(out), ldo, _ptr(kopt), _stream())
+    return (out, kopt) if want_k else out
 
 
 # ------------------------------------------------------------------------------------------------
