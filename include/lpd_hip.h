@@ -436,6 +436,39 @@ int lpd_morton_sort(const float* xyz, float* out, int32_t* perm, int B, int N, v
 int lpd_local_features(const float* xyz, int ldx, const int32_t* idx, int B, int N, int K, const int32_t* cand, int ncand, unsigned sel,
                        int copy_xyz, float* out, int ldo, int32_t* kopt, void* stream);
 
+/*
+ * Submaps from raw scans (csrc/lpd_submap.hip): a ragged batch of B clouds of any length becomes [B][N][3] model input in one launch --
+ * a voxel-grid average whose cell size is searched so that the number of occupied cells lands just under N, filled up to exactly N
+ * with raw points, shifted to zero mean and scaled into [-1, 1].  The reference has no counterpart (its submaps come from an offline
+ * preprocessing step that is not part of it); this comment is the specification.
+ *   points   [rows][ld] fp32, ld >= 3, three coordinates used; finite
+ *   offsets  DEVICE int32 [B+1], ascending: cloud b is rows offsets[b] .. offsets[b+1]-1; 1 <= length <= 2^20.  A cloud whose offsets
+ *            break this (negative, empty, longer) is not read: its rows, counts and xform are 0 and its info is (-1, 0, 0, 0).
+ *   out      [B][N][3]     info [B][4] int32 = (j*, M, n, 0)     xform [B][4] = (mean_x, mean_y, mean_z, r)
+ *   counts   [B][N] int32 or NULL: points per cell on rows 0 .. M-1 (a density weight), 0 on the fill rows (their marker)
+ * For one cloud of n points x_i and the target N, 128 <= N <= 4096; fp32 arithmetic, every operation rounded once (no contraction),
+ * unless stated otherwise:
+ *  1 Box.     mn_c = min_i x_ic,  E = max_c (max_i x_ic - mn_c).
+ *  2 Ladder.  R_j = 1024 * 2^(-j/16) cells per E, j = 0 .. 127: the fp32 literal of 2^(-(j mod 16)/16) times 1024 times
+ *             2^(-(j div 16)) (both exact).  s_j = R_j / E, one IEEE division per cloud and rung; E == 0: s_j = 0.
+ *             Cell of a point: q_c = (uint32) min(max((x_c - mn_c) * s_j, 0), 1023); key = the 30-bit Morton interleave of q
+ *             (x in bit 0, y in bit 1, z in bit 2 of each triple, as lpd_morton_sort).
+ *  3 Search.  count(j) = number of distinct keys.  lo = -1, hi = 127; while hi - lo > 1: mid = (lo + hi) / 2; count(mid) <= N ?
+ *             hi = mid : lo = mid.  j* = hi after 7 steps.  count is NOT monotone in j: j* is the outcome of this bisection, not a
+ *             minimum.  Rung 127 has at most 5 cells per axis (125 <= N), so the search cannot fail: hence N >= 128.
+ *  4 Cells.   The M = count(j*) cells in ascending key order are rows 0 .. M-1.  u_c = rint((x_c - mn_c) * f), f = 2^20 / E (0 if
+ *             E == 0), half to even; S_c = sum of u_c in unsigned 64-bit integers, m = number of points of the cell;
+ *             row_c = mn_c + (float)((double)S_c / (double)m) * (E * 2^-20).  Integer sums: exact in any order.
+ *  5 Fill.    Rows M + p, p = 0 .. N-M-1, are raw points unchanged: x_i with i = ((2p + 1) * n) / (2 (N - M)), 64-bit floor division.
+ *  6 Normalise (normalize = 1).  mean_c = the fp64 sum of the N rows in a fixed order, divided by N, rounded to fp32; d = row - mean;
+ *             r = max |d| over rows and axes; out = d * (1.0f / r), all zeros if r == 0.  xform = (mean, r): row = out * r + mean.
+ *             normalize = 0: the rows of 4 and 5 are written as they are and xform = (0, 0, 0, 1).
+ * The result does not depend on thread order; rows 0 .. M-1, info and counts do not depend on the order of the raw points either
+ * (the fill rows do, by definition).  No float atomics.  One 1024-thread workgroup per cloud; N > 4096: LPD_ERR_UNSUPPORTED.
+ */
+int lpd_make_submaps(const float* points, int ld, const int32_t* offsets, int B, int N, int normalize, float* out, int32_t* info,
+                     float* xform, int32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -7,6 +7,9 @@ host, and the host does no per-element work.
   load_pc_file / load_pc_files   loading_pointclouds.py:26-47, same return values (numpy float64)
   SubmapStream                   iterator over device batches [B,1,N,3] float32, double-buffered
   get_latent_vectors_from_files  evaluate.get_latent_vectors on a list of file names
+  load_scan_file / ScanStream / get_latent_vectors_from_scans
+                                 the same for RAW scans of any length (no counterpart in the reference): rows of float64 xyz or
+                                 KITTI-style float32 x 4, made into submaps on the device (submap.make_submaps)
   evaluate_model_from_sets       evaluate.evaluate_model on the reference's pickled DATABASE_SETS / QUERY_SETS
 """
 import os
@@ -99,6 +102,131 @@ def get_latent_vectors_from_files(model, filenames, batch_size, dataset_folder="
     try:
         with torch.no_grad():
             for batch in SubmapStream(filenames, batch_size, dataset_folder, dev, num_points):
+                outs.append(model(batch).detach().cpu().numpy().reshape(batch.shape[0], -1))
+    finally:
+        model.train(was_training)
+    return np.concatenate(outs, 0) if outs else np.zeros((0, output_dim), np.float32)
+
+
+def load_scan_file(filename, dataset_folder="", dtype=np.float64, columns=3):
+    """A raw scan of any length: -> [n, columns] of `dtype` (the first three columns are the coordinates; KITTI velodyne files are
+    dtype=np.float32, columns=4), or an empty array when the file is empty or not a whole number of rows."""
+    pc = np.fromfile(os.path.join(dataset_folder, filename), dtype=dtype)
+    if columns < 3 or pc.shape[0] == 0 or pc.shape[0] % columns:
+        return np.array([])
+    return np.reshape(pc, (pc.shape[0] // columns, columns))
+
+
+class ScanStream:
+    """The ragged sibling of SubmapStream: for batch in ScanStream(files, 32, folder, device): batch is a float32 CUDA tensor
+    [b,1,N,3] of submaps made on the device from b raw scans of any length (submap.make_submaps; `last` holds the whole result of
+    the batch just yielded).  Files are rows of `columns` values of `dtype`; a file that is empty, not a whole number of rows or
+    longer than 2^20 rows is skipped.  Two pinned byte buffers and a copy stream, as SubmapStream; the buffers are sized from the
+    byte sizes of the first batch's files and grow when a later batch needs more.  float64 rows are narrowed on the device
+    (lpd_f64_to_f32); float32 rows go to the kernel as they are, with ld = columns."""
+
+    def __init__(self, filenames, batch_size, dataset_folder="", device=None, num_points=NUM_POINTS, dtype=np.float64, columns=3,
+                 normalize=True):
+        self.files = list(filenames)
+        self.bs, self.folder, self.N = int(batch_size), dataset_folder, int(num_points)
+        self.dtype, self.columns, self.normalize = np.dtype(dtype), int(columns), bool(normalize)
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or self.columns < 3:
+            raise ValueError(f"ScanStream: rows of >= 3 float64 or float32 values, got {self.columns} x {self.dtype}")
+        if not ops.SUBMAP_MIN_N <= self.N <= ops.SUBMAP_MAX_N:
+            raise ValueError(f"ScanStream: num_points={self.N} outside {ops.SUBMAP_MIN_N} .. {ops.SUBMAP_MAX_N}")
+        self.row_bytes = self.columns * self.dtype.itemsize
+        self.device = device
+        first = sum(self._file_bytes(f) for f in self.files[:self.bs])
+        self.host = [self._host_buffer(max(first, self.row_bytes)) for _ in range(2)]
+        self.staged = [None, None]
+        self.grown = 0            # how often a host buffer had to grow
+        self.last = None
+
+    def _file_bytes(self, f):
+        try:
+            return os.path.getsize(os.path.join(self.folder, f))
+        except OSError:
+            return 0
+
+    @staticmethod
+    def _host_buffer(nbytes):
+        buf = torch.empty((int(nbytes),), dtype=torch.uint8)
+        return buf.pin_memory() if torch.cuda.is_available() else buf
+
+    def _read(self, slot, start):
+        """read up to batch_size valid scans starting at file index `start` into host buffer `slot`, growing it when the files need
+        more; -> (lengths, next file index).  Host work only."""
+        lengths, used, i = [], 0, start
+        while len(lengths) < self.bs and i < len(self.files):
+            path = os.path.join(self.folder, self.files[i])
+            i += 1
+            nbytes = self._file_bytes(self.files[i - 1])
+            rows = nbytes // self.row_bytes
+            if nbytes == 0 or nbytes % self.row_bytes or rows > ops.SUBMAP_MAX_POINTS:
+                continue
+            if used + nbytes > self.host[slot].numel():
+                bigger = self._host_buffer(max(used + nbytes, self.host[slot].numel() * 3 // 2))
+                bigger[:used] = self.host[slot][:used]
+                self.host[slot] = bigger
+                self.grown += 1
+            with open(path, "rb") as fh:
+                got = fh.readinto(memoryview(self.host[slot].numpy())[used:used + nbytes])
+            if got != nbytes:
+                continue
+            lengths.append(rows)
+            used += nbytes
+        return lengths, i
+
+    def _stage(self, slot, start):
+        self.ready[slot].synchronize()        # the previous H2D copy out of this pinned buffer has left the host
+        lengths, i = self._read(slot, start)
+        if lengths:
+            used = sum(lengths) * self.row_bytes
+            if self.staged[slot] is None or self.staged[slot].numel() < used:
+                self.free[slot].synchronize()     # nobody reads the old device buffer any more
+                self.staged[slot] = torch.empty((max(used, self.host[slot].numel()),), dtype=torch.uint8, device=self.device)
+                self.free[slot].record(self.main)     # whatever used this memory before was enqueued on the main stream before now
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(self.free[slot])
+                self.staged[slot][:used].copy_(self.host[slot][:used], non_blocking=True)
+                self.ready[slot].record(self.copy_stream)
+        return lengths, i
+
+    def __iter__(self):
+        from . import submap
+        self.device = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.ready = [torch.cuda.Event(), torch.cuda.Event()]
+        self.free = [torch.cuda.Event(), torch.cuda.Event()]
+        self.main = main = torch.cuda.current_stream(self.device)
+        for ev in self.free:
+            ev.record(main)
+        tdtype = torch.float64 if self.dtype == np.dtype(np.float64) else torch.float32
+        slot, pos = 0, 0
+        lengths, pos = self._stage(slot, pos)
+        while lengths:
+            other = slot ^ 1
+            nxt, pos = self._stage(other, pos) if pos < len(self.files) else ([], pos)
+            main.wait_event(self.ready[slot])
+            rows = self.staged[slot][:sum(lengths) * self.row_bytes].view(tdtype).view(-1, self.columns)
+            self.last = submap.make_submaps(rows, lengths, self.N, self.normalize, check_finite=False)
+            self.free[slot].record(main)
+            yield self.last.x
+            slot, lengths = other, nxt
+
+
+def get_latent_vectors_from_scans(model, filenames, batch_size, dataset_folder="", output_dim=256, num_points=NUM_POINTS,
+                                  dtype=np.float64, columns=3, normalize=True):
+    """get_latent_vectors_from_files for raw scans of any length: eval mode, no_grad, batches of `batch_size` scans streamed from
+    disk and made into submaps on the device (ScanStream), ragged tail, the previous train/eval mode restored afterwards;
+    -> numpy [n_ok, output_dim]."""
+    was_training = model.training
+    model.eval()
+    outs = []
+    dev = next(model.parameters()).device
+    try:
+        with torch.no_grad():
+            for batch in ScanStream(filenames, batch_size, dataset_folder, dev, num_points, dtype, columns, normalize):
                 outs.append(model(batch).detach().cpu().numpy().reshape(batch.shape[0], -1))
     finally:
         model.train(was_training)

@@ -1114,6 +1114,68 @@ def local_features(xyz_rows, idx, B, N, *, candidates=None, columns=range(10), c
     return (out, kopt) if want_k else out
 
 
+SUBMAP_MIN_N, SUBMAP_MAX_N, SUBMAP_MAX_POINTS = 128, 4096, 1 << 20
+
+
+def check_submap_lengths(lengths, rows=None, what="make_submaps"):
+    """Host check of the per-cloud point counts of a ragged batch: each in 1 .. 2^20, and their sum within `rows` when given."""
+    total = 0
+    for b, n in enumerate(lengths):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"{what}: cloud {b} has {n} points (offsets must ascend and no scan may be empty)")
+        if n > SUBMAP_MAX_POINTS:
+            raise ValueError(f"{what}: cloud {b} has {n} points; at most 2^20 per cloud")
+        total += n
+    if rows is not None and total > rows:
+        raise ValueError(f"{what}: the clouds hold {total} rows, the points tensor {rows}")
+    return total
+
+
+def _make_submaps(points, offsets, B, N, normalize, want_counts, out):
+    """The launch alone (tensors and offsets already checked): -> (out [B,N,3], info [B,4] int32, xform [B,4], counts [B,N] | None)"""
+    dev = points.device
+    if out is None:
+        out = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    xform = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, N), dtype=torch.int32, device=dev) if want_counts else None
+    lib = _lib.load()
+    _call(f"make_submaps[n={N}]", lib.lpd_make_submaps, _ptr(points), points.stride(0), _ptr(offsets), B, N, int(bool(normalize)), _ptr(out),
+          _ptr(info), _ptr(xform), _ptr(counts), _stream())
+    return out, info, xform, counts
+
+
+def make_submaps(points, offsets, B, N, normalize=True, want_counts=False, out=None):
+    """Raw scans -> submaps (lpd_make_submaps; definition in include/lpd_hip.h): points [rows, >=3] fp32 with contiguous rows (a
+    KITTI-style [rows, 4] tensor goes in as it is), offsets [B+1] int32 on the device, cloud b = rows offsets[b] .. offsets[b+1]-1
+    with 1 .. 2^20 points each -> (out [B,N,3], info [B,4] int32 = (level, cells, n, 0), xform [B,4] = (centre, scale), counts [B,N]
+    int32 or None), 128 <= N <= 4096.  The offsets are read back and checked on the host (one small copy): the kernel trusts them.
+    out: a contiguous [B,N,3] (or [B,1,N,3]) tensor to write into."""
+    _req(points, "points")
+    _req(offsets, "offsets", torch.int32)
+    B, N = int(B), int(N)
+    if not SUBMAP_MIN_N <= N <= SUBMAP_MAX_N:
+        raise ValueError(f"make_submaps: N={N} outside {SUBMAP_MIN_N} .. {SUBMAP_MAX_N}")
+    ld = _rows(points, "points")
+    if points.shape[1] < 3 or ld < 3:
+        raise ValueError(f"make_submaps: points must be [rows, >=3], got {tuple(points.shape)}")
+    if B < 1 or offsets.dim() != 1 or offsets.numel() != B + 1:
+        raise ValueError(f"make_submaps: offsets must hold B+1 = {B + 1} entries, got {tuple(offsets.shape)}")
+    offsets = offsets.contiguous()
+    host = offsets.cpu().tolist()
+    if host[0] < 0:
+        raise ValueError(f"make_submaps: offsets[0] = {host[0]} < 0")
+    check_submap_lengths([host[b + 1] - host[b] for b in range(B)])
+    if host[B] > points.shape[0]:
+        raise ValueError(f"make_submaps: offsets end at row {host[B]}, the points tensor has {points.shape[0]}")
+    if out is not None:
+        _req(out, "out")
+        if out.numel() != B * N * 3 or not out.is_contiguous():
+            raise ValueError(f"make_submaps: out must be a contiguous [B,N,3] tensor, got {tuple(out.shape)}")
+    return _make_submaps(points, offsets, B, N, normalize, want_counts, out)
+
+
 # ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
