@@ -469,6 +469,38 @@ int lpd_local_features(const float* xyz, int ldx, const int32_t* idx, int B, int
 int lpd_make_submaps(const float* points, int ld, const int32_t* offsets, int B, int N, int normalize, float* out, int32_t* info,
                      float* xform, int32_t* counts, void* stream);
 
+/*
+ * Training tuples on the device (csrc/lpd_tuples.hip; arithmetic in csrc/lpd_tuple_math.h): what the reference's Dataset.__getitem__
+ * does in Python per query (util/data.py:56-101 shuffles and set differences; loading_pointclouds.py:50-85 rotation and jitter) as two
+ * launches over tables that stay on the device.
+ *
+ * lpd_sample_items: distinct items drawn uniformly from a union of item lists, or from its complement; one launch, R rows.
+ *   T        number of items, 1 <= T <= 262144 (the membership bitmap and its scanned popcounts are 64 KiB of LDS at the limit)
+ *   off/idx  CSR of n_lists lists over the items: list l = idx[off[l] .. off[l+1]), int32, nnz = entries of idx; duplicates and any
+ *            order allowed.  off is ascending within [0, nnz]; whatever lies outside is clipped to it.
+ *   lists    [R][L] list numbers of row r, -1 = unused slot, 0 <= L <= 64        extra [R][X] single items, -1 = unused, 0 <= X <= 64
+ *   invert   0 or 1        m  samples per row, 1 <= m <= 4096        seed  64 bits        1 <= R <= 65535
+ *   S_r = the union of the row's lists and extras; the pool is S_r (invert = 0) or [0, T) \ S_r (invert = 1); z_0 < ... < z_{c-1} its
+ *   members in ascending order.  count[r] = c;  out[r][j] = z_{perm(j, c, seed, r)} for j < min(m, c),  -1 for c <= j < m.
+ *   perm(., c, seed, r) is a bijection of [0, c) made of 32-bit integer operations only (a 4-round Feistel network with cycle walking);
+ *   csrc/lpd_tuple_math.h is its definition.  A list number outside [0, n_lists) and an item outside [0, T) -- in lists, extra or
+ *   idx -- is IGNORED and never used as an address.  No float arithmetic, no atomics on global memory: equal bits in every launch.
+ *
+ * lpd_gather_tuples: the model's input from the resident table.
+ *   table [T][N][3] contiguous, items [B] int32 on the device, out [B][N][3] (not the table), 1 <= B <= 65535, 1 <= N <= 2^20
+ *   rot   [B][2] = (cos, sin) of the angle of slot b, or NULL:  x' = x c + y s,  y' = -x s + y c,  z' = z  (the reference's pc @ R;
+ *         two products and a sum, each rounded once)
+ *   sigma, clip, seed: then out += delta,  delta_i = clamp(sigma z_i, -clip, clip),  z from Philox4x32-10 with counter
+ *         (point n, slot b, 0, 0) and key (seed low word, seed high word) through Box-Muller (lpd_tuple_math.h).  sigma = 0: no jitter,
+ *         Philox is never evaluated.  sigma >= 0, clip > 0.
+ *   Without rot and with sigma = 0 the output rows are bit-copies of the table rows.  An item outside [0, T) gives a cloud of zeros
+ *   (no jitter either) and is never read.  N % 4 == 0 with 16-byte aligned table / out: 16-byte accesses, one point per thread else.
+ */
+int lpd_sample_items(const int32_t* off, const int32_t* idx, int n_lists, int nnz, int T, const int32_t* lists, int L, const int32_t* extra,
+                     int X, int R, int invert, int m, unsigned long long seed, int32_t* out, int32_t* count, void* stream);
+int lpd_gather_tuples(const float* table, int T, int N, const int32_t* items, int B, const float* rot, float sigma, float clip,
+                      unsigned long long seed, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -8,6 +8,8 @@ AROUND the model call, with plain arguments:
   train_step         train_pointnetvlad.py:121-134   zero_grad / run_model / loss / backward / optimizer.step
   get_latent_vectors evaluate.py:96-159              eval mode, batched forward with a ragged tail, numpy out,
                                                      model.train() afterwards
+  run_model_feed /   the same two on a feed that lpdnet_hip.tuples.TupleBank sampled, gathered and augmented on the device
+  train_step_from_bank                               (util/data.py:56-101, 190-271 and loading_pointclouds.py:50-85 on the host there)
 and the two "next" rows of SURVEY.md section 8f that sit right behind them:
   get_recall         evaluate.py:162-206             Recall@N / top-1 similarity / one-percent recall of one (database run,
                                                      query run) pair; the KDTree per pair becomes one GPU top-k launch
@@ -49,6 +51,37 @@ def train_step(model, optimizer, queries, positives, negatives, other_neg, *, ma
     model.train()
     optimizer.zero_grad()
     q, p, n, o = run_model(model, queries, positives, negatives, other_neg)
+    fn = L.quadruplet_loss if loss_function == "quadruplet" else L.triplet_loss_wrapper
+    loss = fn(q, p, n, o, margin_1, margin_2, use_min=use_min, lazy=lazy, ignore_zero_loss=ignore_zero_loss)
+    loss.backward()
+    optimizer.step()
+    return loss
+
+
+def run_model_feed(model, feed, bq, P, Ng, require_grad=True, output_dim=256):
+    """run_model on a feed that is already assembled on the device (tuples.TupleBank.assemble): feed [bq * (2+P+Ng), 1, N, 3] fp32
+    in the tuple order q, pos, neg, other -> (q [bq,1,D], pos [bq,P,D], neg [bq,Ng,D], other [bq,1,D])."""
+    if feed.shape[0] != bq * (2 + P + Ng):
+        raise ValueError(f"run_model_feed: feed holds {feed.shape[0]} clouds, bq * (2 + P + Ng) = {bq * (2 + P + Ng)}")
+    if require_grad:
+        out = model(feed)
+    else:
+        with torch.no_grad():
+            out = model(feed)
+    out = out.view(bq, -1, output_dim)
+    return torch.split(out, [1, P, Ng, 1], dim=1)
+
+
+def train_step_from_bank(model, optimizer, bank, query_items, P, Ng, seed, hard=None, rotate=False, jitter=False, *, margin_1=0.5,
+                         margin_2=0.2, loss_function="quadruplet", use_min=True, lazy=True, ignore_zero_loss=False):
+    """train_step fed from a resident tuples.TupleBank: query_items are host integers; the tuples are sampled (bank.sample), gathered
+    and augmented (bank.assemble) on the device, then run_model_feed / loss / backward / optimizer.step as train_step does.  `seed`
+    (e.g. the iteration number) drives the sampling, the rotation angles and the jitter.  Returns the loss tensor."""
+    model.train()
+    optimizer.zero_grad()
+    items = bank.sample(query_items, P, Ng, seed, hard=hard)
+    feed = bank.assemble(items, rotate=rotate, jitter=jitter, seed=seed)
+    q, p, n, o = run_model_feed(model, feed, items.shape[0], P, Ng)
     fn = L.quadruplet_loss if loss_function == "quadruplet" else L.triplet_loss_wrapper
     loss = fn(q, p, n, o, margin_1, margin_2, use_min=use_min, lazy=lazy, ignore_zero_loss=ignore_zero_loss)
     loss.backward()

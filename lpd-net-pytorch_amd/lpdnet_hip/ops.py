@@ -1176,6 +1176,82 @@ def make_submaps(points, offsets, B, N, normalize=True, want_counts=False, out=N
     return _make_submaps(points, offsets, B, N, normalize, want_counts, out)
 
 
+TUPLE_MAX_ITEMS, TUPLE_MAX_SAMPLES, TUPLE_MAX_LISTS, TUPLE_MAX_ROWS = 262144, 4096, 64, 65535      # csrc/lpd_tuple_math.h
+
+
+def sample_items(off, idx, T, lists, extra, m, invert, seed):
+    """Distinct items drawn uniformly from a union of item lists or from its complement (lpd_sample_items; definition in
+    include/lpd_hip.h): off [n_lists+1] / idx [nnz] the int32 CSR of the lists over T items, lists [R, L] list numbers per row
+    (-1 = unused), extra [R, X] single items (-1 = unused) or None, invert 0 / 1, m samples per row, seed 64 bits.
+    -> (out [R, m] int32, -1 behind the pool's size; count [R] int32, the pool's size).  Everything stays on the device."""
+    _req(off, "off", torch.int32)
+    _req(idx, "idx", torch.int32)
+    _req(lists, "lists", torch.int32)
+    _req(extra, "extra", torch.int32)
+    T, m = int(T), int(m)
+    if off is None or idx is None or lists is None:
+        raise TypeError("sample_items: off, idx and lists are tensors (an empty lists tensor is [R, 0])")
+    if off.dim() != 1 or off.numel() < 1 or idx.dim() != 1:
+        raise ValueError(f"sample_items: off must be [n_lists+1] and idx [nnz], got {tuple(off.shape)} and {tuple(idx.shape)}")
+    if lists.dim() != 2 or not 1 <= lists.shape[0] <= TUPLE_MAX_ROWS or lists.shape[1] > TUPLE_MAX_LISTS:
+        raise ValueError(f"sample_items: lists must be [R, L] with 1 <= R <= {TUPLE_MAX_ROWS}, L <= {TUPLE_MAX_LISTS}, got {tuple(lists.shape)}")
+    R, L = lists.shape
+    X = 0
+    if extra is not None:
+        if extra.dim() != 2 or extra.shape[0] != R or extra.shape[1] > TUPLE_MAX_LISTS:
+            raise ValueError(f"sample_items: extra must be [R, X] with R = {R}, X <= {TUPLE_MAX_LISTS}, got {tuple(extra.shape)}")
+        X = extra.shape[1]
+        extra = extra.contiguous() if X else None
+    if not 1 <= T <= TUPLE_MAX_ITEMS:
+        raise ValueError(f"sample_items: T={T} outside 1 .. {TUPLE_MAX_ITEMS}")
+    if not 1 <= m <= TUPLE_MAX_SAMPLES:
+        raise ValueError(f"sample_items: m={m} outside 1 .. {TUPLE_MAX_SAMPLES}")
+    if invert not in (0, 1, False, True):
+        raise ValueError(f"sample_items: invert={invert!r} (0 or 1)")
+    off, idx = off.contiguous(), idx.contiguous()
+    lists = lists.contiguous() if L else None
+    out = torch.empty((R, m), dtype=torch.int32, device=off.device)
+    count = torch.empty((R,), dtype=torch.int32, device=off.device)
+    lib = _lib.load()
+    _call("sample_items", lib.lpd_sample_items, _ptr(off), _ptr(idx) if idx.numel() else None, off.numel() - 1, idx.numel(), T, _ptr(lists), L,
+          _ptr(extra), X, R, int(invert), m, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _ptr(count), _stream())
+    return out, count
+
+
+def gather_tuples(table, items, rot=None, sigma=0.0, clip=0.05, seed=0, out=None):
+    """The model's input from the resident cloud table (lpd_gather_tuples; definition in include/lpd_hip.h): table [T, N, 3] fp32
+    contiguous, items [B] int32 on the device, rot [B, 2] = (cos, sin) per slot or None, jitter clamp(sigma * z, -clip, clip) with z
+    from Philox (sigma = 0: none) -> out [B, N, 3].  An item outside [0, T) gives zeros.  out: a contiguous tensor of B*N*3 elements
+    (e.g. [B, 1, N, 3]) to write into."""
+    _req(table, "table")
+    _req(items, "items", torch.int32)
+    _req(rot, "rot")
+    if table.dim() != 3 or table.shape[2] != 3 or not table.is_contiguous() or table.shape[0] < 1 or table.shape[1] < 1:
+        raise ValueError(f"gather_tuples: table must be a contiguous [T, N, 3] tensor, got {tuple(table.shape)}")
+    T, N = table.shape[:2]
+    if items.dim() != 1 or not 1 <= items.numel() <= TUPLE_MAX_ROWS:
+        raise ValueError(f"gather_tuples: items must be [B] with 1 <= B <= {TUPLE_MAX_ROWS}, got {tuple(items.shape)}")
+    items = items.contiguous()
+    B = items.numel()
+    if rot is not None:
+        if tuple(rot.shape) != (B, 2):
+            raise ValueError(f"gather_tuples: rot must be [B, 2] = ({B}, 2), got {tuple(rot.shape)}")
+        rot = rot.contiguous()
+    sigma, clip = float(sigma), float(clip)
+    if not sigma >= 0.0 or not clip > 0.0:
+        raise ValueError(f"gather_tuples: sigma={sigma} clip={clip} (sigma >= 0, clip > 0)")
+    if out is None:
+        out = torch.empty((B, N, 3), dtype=torch.float32, device=table.device)
+    else:
+        _req(out, "out")
+        if out.numel() != B * N * 3 or not out.is_contiguous():
+            raise ValueError(f"gather_tuples: out must be a contiguous tensor of B*N*3 elements, got {tuple(out.shape)}")
+    lib = _lib.load()
+    _call("gather_tuples", lib.lpd_gather_tuples, _ptr(table), T, N, _ptr(items), B, _ptr(rot), sigma, clip, int(seed) & 0xFFFFFFFFFFFFFFFF,
+          _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
