@@ -501,6 +501,36 @@ int lpd_sample_items(const int32_t* off, const int32_t* idx, int n_lists, int nn
 int lpd_gather_tuples(const float* table, int T, int N, const int32_t* items, int B, const float* rot, float sigma, float clip,
                       unsigned long long seed, float* out, void* stream);
 
+/*
+ * Place lists from positions (csrc/lpd_places.hip; the predicate in csrc/lpd_places_math.h): which database items lie within a radius
+ * of each query position, per database segment, as sorted CSR rows.  What the reference's generating_queries/ scripts make on the
+ * host with sklearn's KDTree.query_radius over (northing, easting): generate_training_tuples_baseline.py:52-72 at r = 10 m (positives)
+ * and r = 50 m (the non-negatives), generate_test_sets.py:99-109 at r = 25 m (the truth lists of the evaluation).
+ *   qpos     [Q][2] float64 query positions         dpos  [D][2] float64 database positions; both 16-byte aligned
+ *   seg_off  DEVICE int32 [S+1], rising from 0 to D: segment s (one database run; S = 1 for training) is the items
+ *            seg_off[s] .. seg_off[s+1]-1.  Whatever lies outside [0, D] is clipped to it; nothing outside the table is read.
+ *   r        the radius, finite, >= 0
+ * Row g * S + s (query g, segment s) holds, in ascending order, the LOCAL indices j - seg_off[s] of the items j of segment s with
+ *     dx = qpos[g][0] - dpos[j][0];   dy = qpos[g][1] - dpos[j][1];   (dx * dx) + (dy * dy) <= r * r
+ * in float64, every operation rounded once, nothing contracted, r * r ONE product.  A NaN on either side is never a member (nor is
+ * an infinite coordinate); (a - b)^2 == (b - a)^2 exactly, so membership is symmetric in the two positions.  Float64 is part of the
+ * definition: at a UTM northing of 5.7e6 an fp32 ulp is 0.5 m.  On boundary points -- offsets (6, 8), (8, 6), (10, 0) at r = 10 -- the
+ * rule includes the item, as KDTree.query_radius does.
+ *   skip_seg   [Q] int32 or NULL: skip_seg[g] == s makes row (g, s) empty (generate_test_sets.py:102 `if i == j: continue`); -1 = none
+ *   self_item  [Q] int32 or NULL: the GLOBAL database index self_item[g] is left out of the rows of query g (np.setdiff1d(ind_nn[i],
+ *              [i]) of generate_training_tuples_baseline.py:59); -1 = none
+ * lpd_radius_count writes counts [Q * S] int32, the row lengths.  lpd_radius_fill takes row_off [Q * S + 1], the exclusive scan of
+ * the counts (the caller's: torch.cumsum in lpdnet_hip/ops.py), and writes idx [nnz], nnz = row_off[Q * S]; an entry whose place
+ * falls outside [0, nnz) -- a row_off that is not that scan -- is dropped, not written.  Both calls run one kernel on the same
+ * predicate, so the counts and the fill agree; the order within a row comes from the kernel's construction (candidates in
+ * ascending order, __ballot and a popcount of the lanes below), not from a sort.  No atomics: the same bits in every launch.
+ * Limits: 1 <= S <= 4096, 0 <= Q, D <= 2^22, Q * S < 2^31.  Q == 0 launches nothing.
+ */
+int lpd_radius_count(const double* qpos, int Q, const double* dpos, int D, const int32_t* seg_off, int S, double r, const int32_t* skip_seg,
+                     const int32_t* self_item, int32_t* counts, void* stream);
+int lpd_radius_fill(const double* qpos, int Q, const double* dpos, int D, const int32_t* seg_off, int S, double r, const int32_t* skip_seg,
+                    const int32_t* self_item, const int32_t* row_off, int32_t* idx, int nnz, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -96,6 +96,8 @@ SIGNATURES = {
     "lpd_sample_items": [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_ulonglong, _c_p, _c_p,
                          _c_p],
     "lpd_gather_tuples": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_f, _c_f, ctypes.c_ulonglong, _c_p, _c_p],
+    "lpd_radius_count": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p],
+    "lpd_radius_fill": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p],
     "lpd_colstats": [_c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p],
     "lpd_bn_finalize": [_c_p, _c_p, ctypes.c_double, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p],
     "lpd_affine_act": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p],

@@ -382,8 +382,17 @@ def _evaluate_counts(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num, pa
         empty = np.nonzero(np.diff(off)[pairs[:, col]] == 0)[0]
         if empty.size:
             raise ValueError(f"evaluate: {what} run {int(pairs[empty[0], col])} is empty")
-    truth_off, truth_idx = build_truth_csr(QUERY_SETS, np.diff(q_off), d_off.size - 1, pairs)
-    r = ops.recall_pairs(Q, D, q_off.astype(np.int32), d_off.astype(np.int32), pairs, truth_off, truth_idx, recall_num)
+    from .places import TruthTable
+    resident = isinstance(QUERY_SETS, TruthTable)      # the truth lists are on the device already (places.evaluation_truth)
+    if resident:
+        if QUERY_SETS.q_counts != np.diff(q_off).tolist() or QUERY_SETS.n_db_runs != d_off.size - 1:
+            raise ValueError(f"evaluate: the TruthTable was made for query runs of {QUERY_SETS.q_counts} rows and {QUERY_SETS.n_db_runs} "
+                             f"database runs; the descriptors have {np.diff(q_off).tolist()} and {d_off.size - 1}")
+        truth_off, truth_idx = QUERY_SETS.truth_off.to(dev), QUERY_SETS.truth_idx.to(dev)
+    else:
+        truth_off, truth_idx = build_truth_csr(QUERY_SETS, np.diff(q_off), d_off.size - 1, pairs)
+    r = ops.recall_pairs(Q, D, q_off.astype(np.int32), d_off.astype(np.int32), pairs, truth_off, truth_idx, recall_num,
+                         truth_on_device=resident)
     first, sim = r.first.cpu().numpy(), r.top1_sim.cpu().numpy()
     return (r.hist.cpu().numpy(), r.n_eval.cpu().numpy(), r.n_onepct.cpu().numpy(), first, sim, r.out_off)
 
@@ -394,7 +403,8 @@ def evaluate_pairs(DATABASE_VECTORS, QUERY_VECTORS, QUERY_SETS, recall_num=RECAL
 
     DATABASE_VECTORS / QUERY_VECTORS: lists of per-run [n, D] descriptors (numpy, as get_latent_vectors returns them, or tensors), or
     a resident (CUDA table, run offsets) tuple as embed_runs returns it.  QUERY_SETS[n][i][m] = true neighbours of query i of run n in
-    run m.  pairs: rows (m, n); default every m != n over range(len(QUERY_SETS)), m outer (the reference's loop order).
+    run m -- or a places.TruthTable (places.evaluation_truth: the same lists made on the device from the positions), whose arrays
+    are used where they are instead of the walk over the nested structure.  pairs: rows (m, n); default every m != n over range(len(QUERY_SETS)), m outer (the reference's loop order).
     -> list, one entry per pair: (recall [recall_num] cumulative percent, top-1 similarity list, one-percent recall), identical to
     get_recall(m, n, ...).
 

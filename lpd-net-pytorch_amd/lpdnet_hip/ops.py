@@ -1252,6 +1252,65 @@ def gather_tuples(table, items, rot=None, sigma=0.0, clip=0.05, seed=0, out=None
     return out
 
 
+PLACES_MAX_ITEMS, PLACES_MAX_SEGMENTS, PLACES_CHUNK = 1 << 22, 4096, 1024      # csrc/lpd_places_math.h
+
+
+def radius_lists(qpos, dpos, radius, seg_off=None, skip_seg=None, self_item=None):
+    """The database items within `radius` of every query position, per database segment, as sorted CSR rows (lpd_radius_count, a
+    torch.cumsum, lpd_radius_fill; definition in include/lpd_hip.h): qpos [Q, 2] / dpos [D, 2] float64 on the device; seg_off [S+1]
+    int32 (host array or tensor, checked on the host: rising from 0 to D; None = one segment); skip_seg / self_item [Q] int32 on
+    the device or None.  -> (off int32 [Q*S+1], idx int32 [off[-1]], counts int32 [Q*S]) on the device; row g * S + s holds ascending
+    indices local to segment s.  The total is read back once (the size of idx); 2^31 entries or more raise ValueError."""
+    _req(qpos, "qpos", torch.float64)
+    _req(dpos, "dpos", torch.float64)
+    _req(skip_seg, "skip_seg", torch.int32)
+    _req(self_item, "self_item", torch.int32)
+    if qpos is None or dpos is None:
+        raise TypeError("radius_lists: qpos and dpos are tensors")
+    if qpos.dim() != 2 or qpos.shape[1] != 2 or dpos.dim() != 2 or dpos.shape[1] != 2:
+        raise ValueError(f"radius_lists: positions must be [Q, 2] and [D, 2], got {tuple(qpos.shape)} and {tuple(dpos.shape)}")
+    Q, D = qpos.shape[0], dpos.shape[0]
+    if Q > PLACES_MAX_ITEMS or D > PLACES_MAX_ITEMS:
+        raise ValueError(f"radius_lists: Q={Q} D={D}; at most {PLACES_MAX_ITEMS} each")
+    radius = float(radius)
+    if not (radius >= 0.0 and radius != float("inf")):
+        raise ValueError(f"radius_lists: radius={radius} (finite, >= 0)")
+    if seg_off is None:
+        host = [0, D]
+    else:
+        host = seg_off.detach().cpu().tolist() if isinstance(seg_off, torch.Tensor) else [int(v) for v in seg_off]
+    S = len(host) - 1
+    if not 1 <= S <= PLACES_MAX_SEGMENTS:
+        raise ValueError(f"radius_lists: {S} segments; 1 .. {PLACES_MAX_SEGMENTS}")
+    if host[0] != 0 or host[-1] != D or any(b < a for a, b in zip(host, host[1:])):
+        raise ValueError(f"radius_lists: seg_off must rise from 0 to D = {D}")
+    if Q * S >= 2 ** 31:
+        raise ValueError(f"radius_lists: Q * S = {Q * S} rows; fewer than 2^31")
+    for t, name in ((skip_seg, "skip_seg"), (self_item, "self_item")):
+        if t is not None and tuple(t.shape) != (Q,):
+            raise ValueError(f"radius_lists: {name} must be [Q] = ({Q},), got {tuple(t.shape)}")
+    dev = qpos.device
+    counts = torch.empty((Q * S,), dtype=torch.int32, device=dev)
+    if Q == 0:
+        return torch.zeros((1,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev), counts
+    qpos, dpos = qpos.contiguous(), dpos.contiguous()
+    skip_seg = None if skip_seg is None else skip_seg.contiguous()
+    self_item = None if self_item is None else self_item.contiguous()
+    seg = torch.tensor(host, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    head = (_ptr(qpos), Q, _ptr(dpos) if D else None, D, _ptr(seg), S, radius, _ptr(skip_seg), _ptr(self_item))
+    _call("radius_count", lib.lpd_radius_count, *head, _ptr(counts), _stream())
+    off64 = torch.zeros((Q * S + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=off64[1:])
+    nnz = int(off64[-1].item())      # the one read-back: the size of idx
+    if nnz >= 2 ** 31:
+        raise ValueError(f"radius_lists: {nnz} entries; fewer than 2^31")
+    off = off64.to(torch.int32)
+    idx = torch.empty((nnz,), dtype=torch.int32, device=dev)
+    _call("radius_fill", lib.lpd_radius_fill, *head, _ptr(off), _ptr(idx) if nnz else None, nnz, _stream())
+    return off, idx, counts
+
+
 # ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
@@ -2214,7 +2273,7 @@ def _recall_table(X, name):
     return Xp, dimp
 
 
-def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=False):
+def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=False, truth_on_device=False):
     """The recall evaluation of evaluate.py:33-93 in ONE launch (lpd_recall_pairs, include/lpd_hip.h): for every (database run m,
     query run n) row of `pairs` and every query i of run n, the min(k, Nd_m) nearest rows of run m (squared L2 with the arithmetic of
     retrieval_topk, ties -> lower index) scored against the truth list QUERY_SETS[n][i][m].
@@ -2222,6 +2281,8 @@ def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=F
     Q [sum Nq, dim], D [sum Nd, dim]: CUDA fp32, all runs concatenated (rows with a leading dimension allowed); q_off [Rq + 1],
     d_off [Rd + 1]: run offsets (0 first); pairs [P, 2] = (m, n); truth_off [q_off[-1] * Rd + 1] / truth_idx: the truth lists as CSR
     (list of global query row g and run m at truth_off[g * Rd + m]).  Index arrays: int32 numpy arrays or tensors (checked on the host).
+    truth_on_device=True: truth_off / truth_idx are int32 tensors on Q's device made by radius_lists (places.TruthTable) and are
+    used where they are -- only their sizes are checked, their contents are a scan by construction.
     -> RecallPairs: per (pair, query) row, pair p at rows out_off[p] .. out_off[p + 1] (query order):
          first int32 (-1: no truth; k: no hit in the ranks; else the rank of the first true neighbour), one_pct uint8,
          top1_sim fp32 (dot product with the rank-0 row), topk_idx int32 [.., k] (-1 past min(k, Nd); only with want_topk, else None);
@@ -2236,7 +2297,14 @@ def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=F
         raise ValueError(f"recall_pairs: k={k} (1..{RECALL_KMAX})")
     qo, do = _index_array(q_off, "q_off", 1), _index_array(d_off, "d_off", 1)
     pr = _index_array(pairs, "pairs", 2)
-    to, ti = _index_array(truth_off, "truth_off", 1), _index_array(truth_idx, "truth_idx", 1)
+    if truth_on_device:
+        _req(truth_off, "truth_off", torch.int32)
+        _req(truth_idx, "truth_idx", torch.int32)
+        if truth_off is None or truth_idx is None or truth_off.dim() != 1 or truth_idx.dim() != 1 or truth_off.device != Q.device \
+                or truth_idx.device != Q.device:
+            raise ValueError("recall_pairs: truth_on_device takes 1-D int32 tensors on the device of Q")
+    else:
+        to, ti = _index_array(truth_off, "truth_off", 1), _index_array(truth_idx, "truth_idx", 1)
     for name, off, rows in (("q_off", qo, Q.shape[0]), ("d_off", do, D.shape[0])):
         if off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] > rows:
             raise ValueError(f"recall_pairs: {name} must rise from 0 to at most the {rows} table rows")
@@ -2249,7 +2317,10 @@ def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=F
     nq, nd = (qo[n + 1] - qo[n]).astype(np.int64), (do[m + 1] - do[m]).astype(np.int64)
     if (nq == 0).any() or (nd == 0).any():
         raise ValueError("recall_pairs: a pair names an empty run")
-    if to.size != int(qo[-1]) * rd + 1 or to[0] != 0 or (np.diff(to) < 0).any() or to[-1] != ti.size:
+    if truth_on_device:
+        if truth_off.numel() != int(qo[-1]) * rd + 1:
+            raise ValueError("recall_pairs: truth_off must be [q_off[-1] * Rd + 1]")
+    elif to.size != int(qo[-1]) * rd + 1 or to[0] != 0 or (np.diff(to) < 0).any() or to[-1] != ti.size:
         raise ValueError("recall_pairs: truth_off must be [q_off[-1] * Rd + 1], rising from 0 to len(truth_idx)")
     out_off = np.zeros(pr.shape[0] + 1, dtype=np.int64)
     np.cumsum(nq, out=out_off[1:])
@@ -2258,8 +2329,13 @@ def recall_pairs(Q, D, q_off, d_off, pairs, truth_off, truth_idx, k, want_topk=F
         raise ValueError("recall_pairs: more than 2^31 (pair, query) rows")
     dev = Q.device
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev, non_blocking=False)   # noqa: E731
-    q_off_d, d_off_d, pairs_d, out_off_d, to_d = up(qo), up(do), up(pr), up(out_off), up(to)
-    ti_d = up(ti) if ti.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+    q_off_d, d_off_d, pairs_d, out_off_d = up(qo), up(do), up(pr), up(out_off)
+    if truth_on_device:
+        to_d = truth_off.contiguous()
+        ti_d = truth_idx.contiguous() if truth_idx.numel() else torch.zeros((1,), dtype=torch.int32, device=dev)
+    else:
+        to_d = up(to)
+        ti_d = up(ti) if ti.size else torch.zeros((1,), dtype=torch.int32, device=dev)
     first = torch.empty((total,), dtype=torch.int32, device=dev)
     one = torch.empty((total,), dtype=torch.uint8, device=dev)
     sim = torch.empty((total,), dtype=torch.float32, device=dev)

@@ -6,7 +6,8 @@ Replaces what the reference's Dataset.__getitem__ does per query in Python (util
 50-142): shuffle of the `negatives` list, the set difference for `other_neg`, fancy-indexing 22 float64 clouds, cast, collate, copy,
 and the numpy rotation / jitter.
 
-    bank  = TupleBank.from_queries_dict(TRAINING_QUERIES, TRAINING_POINT_CLOUD)        # once
+    bank  = TupleBank.from_queries_dict(TRAINING_QUERIES, TRAINING_POINT_CLOUD)        # once, from the reference's pickle, or
+    bank  = TupleBank.from_positions(TRAINING_POINT_CLOUD, positions)                  # ... from [T, 2] positions (places.py)
     items = bank.sample(query_items, P=2, Ng=18, seed=step)                             # [bq, 2 + P + Ng] int32 on the device
     feed  = bank.assemble(items, rotate=True, jitter=True, seed=step)                   # [bq * (2+P+Ng), 1, N, 3]
 
@@ -80,6 +81,17 @@ class TupleBank:
     SLICE_BYTES = 64 << 20      # host -> device slices of the cloud table
 
     def __init__(self, clouds, positives, near, device=None):
+        self._open(clouds, device)
+        if len(positives) != self.T or len(near) != self.T:
+            raise ValueError(f"TupleBank: {self.T} clouds, {len(positives)} positive lists, {len(near)} near lists")
+        self._set_lists(positives, near)
+        self._upload(clouds)
+        with self._on_device():
+            self.pos_off, self.pos_idx = (torch.from_numpy(a).to(self.device) for a in self._pos_csr)
+            self.near_off, self.near_idx = (torch.from_numpy(a).to(self.device) for a in self._near_csr)
+
+    def _open(self, clouds, device):
+        """the device and the shape of the cloud table: sets T, N, device"""
         if device is None and not torch.cuda.is_available():
             raise LpdHipError("TupleBank: no GPU visible; the tuple bank lives on the MI355X (no CPU fallback)")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -91,10 +103,11 @@ class TupleBank:
         T, N = int(shape[0]), int(shape[1])
         if T > ops.TUPLE_MAX_ITEMS:
             raise ValueError(f"TupleBank: {T} items; at most {ops.TUPLE_MAX_ITEMS}")
-        if len(positives) != T or len(near) != T:
-            raise ValueError(f"TupleBank: {T} clouds, {len(positives)} positive lists, {len(near)} near lists")
         self.T, self.N, self.device = T, N, dev
-        self._set_lists(positives, near)
+
+    def _upload(self, clouds):
+        """the cloud table, in slices"""
+        T, N, dev = self.T, self.N, self.device
         self.table = torch.empty((T, N, 3), dtype=torch.float32, device=dev)
         step = max(1, self.SLICE_BYTES // (N * 3 * 8))
         with self._on_device():
@@ -105,8 +118,6 @@ class TupleBank:
                     ops.f64_to_f32(torch.from_numpy(chunk).to(dev), out=self.table[s:s + step])
                 else:      # float32 rows as they are (on a host-only bank torch narrows float64: the same rounding)
                     self.table[s:s + step].copy_(torch.from_numpy(chunk))
-            self.pos_off, self.pos_idx = (torch.from_numpy(a).to(dev) for a in self._pos_csr)
-            self.near_off, self.near_idx = (torch.from_numpy(a).to(dev) for a in self._near_csr)
 
     def _on_device(self):
         import contextlib
@@ -126,6 +137,28 @@ class TupleBank:
         near[i] = all \\ negatives[i] is derived once, with numpy."""
         positives, near = cls.lists_from_queries_dict(TRAINING_QUERIES)
         return cls(clouds, positives, near, device=device)
+
+    @classmethod
+    def from_positions(cls, clouds, positions, pos_radius=10.0, near_radius=50.0, device=None):
+        """The bank from the items' positions [T, 2] (northing, easting; float64) instead of lists: positives[i] = the items within
+        pos_radius of i without i, near[i] = the items within near_radius, made on the device (places.training_lists: what
+        generate_training_tuples_baseline.py:52-60 searches with a KDTree) and installed as they are -- no Python list, no host CSR
+        (`_pos_csr` / `_near_csr` are None on such a bank).  device="cpu" raises LpdHipError: the lists come from the kernel."""
+        from . import places
+        self = cls.__new__(cls)
+        self._open(clouds, device)
+        if self.device.type != "cuda":
+            raise LpdHipError("TupleBank.from_positions: the place lists come from the MI355X kernel (no CPU fallback)")
+        n = positions.shape[0] if hasattr(positions, "shape") else len(positions)
+        if n != self.T:
+            raise ValueError(f"TupleBank.from_positions: {self.T} clouds, {n} positions")
+        lists = places.training_lists(positions, pos_radius, near_radius, device=self.device)
+        self.pos_off, self.pos_idx, self.pos_len = lists.pos_off, lists.pos_idx, lists.pos_len
+        self.near_off, self.near_idx, self.near_len = lists.near_off, lists.near_idx, lists.near_len
+        self.max_pos, self.max_near = lists.max_pos, lists.max_near
+        self._pos_csr = self._near_csr = None
+        self._upload(clouds)
+        return self
 
     @staticmethod
     def lists_from_queries_dict(TRAINING_QUERIES):
