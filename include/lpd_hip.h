@@ -531,6 +531,61 @@ int lpd_radius_count(const double* qpos, int Q, const double* dpos, int D, const
 int lpd_radius_fill(const double* qpos, int Q, const double* dpos, int D, const int32_t* seg_off, int S, double r, const int32_t* skip_seg,
                     const int32_t* self_item, const int32_t* row_off, int32_t* idx, int nnz, void* stream);
 
+/*
+ * Road removal and range crop for raw scans (csrc/lpd_clean.hip; arithmetic in csrc/lpd_clean_math.h): the step in front of
+ * lpd_make_submaps.  The reference's models are trained on submaps "preprocessed with the road removed" by an offline step that is not
+ * part of it; this comment is the specification, and lpd_clean_math.h settles every detail it leaves open.  A deterministic road-plane
+ * estimator (scored random triples, one least-squares round), a crop, and a stable ragged compaction; no read-back.
+ *   points   [rows][ld] fp32, ld >= 3, three coordinates used; NaN and inf allowed (such rows are not live)
+ *   offsets  DEVICE int32 [B+1]: scan b is rows offsets[b] .. offsets[b+1]-1.  A scan whose offsets are negative, empty, longer than
+ *            max_len (the caller's bound on the longest scan, 1 .. 2^20; it sizes the grid) or end behind `rows` is NOT READ: it keeps
+ *            0 rows, its plane is 0 and its info is (-1, -1, 0, 0).
+ *   prm      LpdCleanParams in HOST memory (read by the call).  0 <= r_min <= r_max <= 512 m; 0 <= H <= 1024; tau, min_det, max_slope
+ *            finite and >= 0; clearance finite; the z limits may be +-inf but not NaN; min_inliers >= 0; refine 0 or 1.
+ * For one scan of n rows, fp32, every operation rounded once, no contraction, IEEE division, every comparison false on NaN:
+ *  1 Live.     x, y, z finite;  r_min*r_min <= (x*x) + (y*y) <= r_max*r_max (each square on the outside ONE product);  z_lo <= z <= z_hi.
+ *  2 Hypotheses h = 0 .. H-1.  (r0, r1, r2, _) = lpd_philox4x32_10(h, b, 0, 0, seed_lo, seed_hi);  rows i_j = ((uint64) r_j * n) >> 32.
+ *              Valid iff the three rows are live and seed_z_lo <= z <= seed_z_hi, and with u = p1 - p0, v = p2 - p0,
+ *              det = (u_x*v_y) - (u_y*v_x):  |det| >= min_det,  a = ((u_z*v_y) - (v_z*u_y)) / det,  b = ((u_x*v_z) - (v_x*u_z)) / det,
+ *              c = z0 - ((a*x0) + (b*y0)),  (a*a) + (b*b) <= max_slope*max_slope,  c finite.  The plane is z = a x + b y + c.
+ *  3 Score.    e_i = z_i - (((a*x_i) + (b*y_i)) + c);  S(h) = number of live rows with fabsf(e_i) <= tau.  h* = the valid h with the
+ *              largest S, ties to the lowest h.  No valid h, or S(h*) < min_inliers: "no road" -- the road rule removes nothing, the
+ *              plane is 0, info = (n_live, -1, the largest S of a valid h or 0, 0).  H = 0: no road step at all, crop only.
+ *  4 Refine (refine = 1, one round).  o = p0 of h*.  Over the inliers of h*: X = (int) rintf((x - o_x) * 1024.0f), clamped to +-2^20,
+ *              Y and Z alike; the nine sums m, SX, SY, SZ, SXX, SXY, SYY, SXZ, SYZ in 64-bit integers (exact in any order); then in
+ *              float64, in the order written in lpd_clean_solve: cxx = SXX - SX*SX/m ..., D = cxx*cyy - cxy*cxy,
+ *              a' = (cxz*cyy - cyz*cxy) / D, b' = (cyz*cxx - cxz*cxy) / D, c' = (SZ - a'*SX - b'*SY) / m,
+ *              c = (float)(o_z + c'/1024 - a'*o_x - b'*o_y); a, b rounded to fp32.  The plane of h* is kept when m < 3, D is not
+ *              positive and finite, or the refined slope breaks max_slope.
+ *  5 Remove.   A live row is removed iff z - (((a*x) + (b*y)) + c) <= clearance: the road and everything under it.  The rows that
+ *              are kept stay in their order (a stable compaction).
+ * lpd_road_planes writes plane [B][4] = (a, b, c, 0) and info [B][4] int32 = (n_live, h* or -1, S(h*), inliers of the final plane);
+ * ws = lpd_road_planes_workspace_bytes(B, H) bytes, 16-byte aligned, the caller's, no state between calls.  The plane depends on the
+ * order of the rows (the triples are drawn by row number); for a given plane, which rows are kept does not.
+ * lpd_clean_count writes counts [B * chunks] int32, chunks = ceil(max_len / LPD_CLEAN_CHUNK): the rows kept in each 1024-row chunk of
+ * each scan.  lpd_clean_fill takes block_off [B * chunks + 1], the exclusive scan of the counts (the caller's: torch.cumsum in
+ * lpdnet_hip/ops.py), and writes out [rows][3] (the kept rows of scan 0, then scan 1, ...: bit-copies), out_offsets [B+1] on the DEVICE
+ * (out_offsets[b] = block_off[b * chunks], out_offsets[B] = block_off[B * chunks]) and, when not NULL, mask [rows] uint8: 1 = kept,
+ * 0 = dropped, for the rows of scans that are read (the others are left as they are).  A place outside [0, rows) -- a block_off that
+ * is not that scan -- is dropped, not written.  plane and info NULL (both): crop only.  Both calls run one kernel on the same
+ * predicate.  Integer atomics only, no float atomics: the same bits in every launch.  1 <= B <= 65535.
+ */
+#define LPD_CLEAN_CHUNK 1024
+typedef struct LpdCleanParams {
+    float r_min, r_max, z_lo, z_hi, seed_z_lo, seed_z_hi, tau, min_det, max_slope, clearance;
+    int32_t H, min_inliers, refine;
+    uint32_t seed_lo, seed_hi;      /* the two words of the 64-bit seed: the Philox key */
+    int32_t reserved;               /* 0 */
+} LpdCleanParams;
+long long lpd_road_planes_workspace_bytes(int B, int H);
+int lpd_road_planes(const float* points, int ld, int rows, const int32_t* offsets, int B, int max_len, const LpdCleanParams* prm,
+                    float* plane, int32_t* info, void* ws, void* stream);
+int lpd_clean_count(const float* points, int ld, int rows, const int32_t* offsets, int B, int max_len, const LpdCleanParams* prm,
+                    const float* plane, const int32_t* info, int32_t* counts, void* stream);
+int lpd_clean_fill(const float* points, int ld, int rows, const int32_t* offsets, int B, int max_len, const LpdCleanParams* prm,
+                   const float* plane, const int32_t* info, const int32_t* block_off, float* out, int32_t* out_offsets,
+                   unsigned char* mask, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

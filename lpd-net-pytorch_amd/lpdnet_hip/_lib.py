@@ -98,6 +98,10 @@ SIGNATURES = {
     "lpd_gather_tuples": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_f, _c_f, ctypes.c_ulonglong, _c_p, _c_p],
     "lpd_radius_count": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p],
     "lpd_radius_fill": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p],
+    "lpd_road_planes_workspace_bytes": [_c_int, _c_int],
+    "lpd_road_planes": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
+    "lpd_clean_count": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
+    "lpd_clean_fill": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
     "lpd_colstats": [_c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p],
     "lpd_bn_finalize": [_c_p, _c_p, ctypes.c_double, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p],
     "lpd_affine_act": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p],
@@ -164,7 +168,7 @@ SIGNATURES = {
 _RESTYPES = {"lpd_last_error": ctypes.c_char_p, "lpd_stat_ws_bytes": ctypes.c_longlong, "lpd_knn_workspace_floats": ctypes.c_longlong,
              "lpd_gemm_prep_b_bytes": ctypes.c_longlong, "lpd_gemm_tn_bf16_ws_floats": ctypes.c_longlong, "lpd_gemm_tn_ws_floats": ctypes.c_longlong,
              "lpd_gemm_tn_act_ws_floats": ctypes.c_longlong,
-             "lpd_edge_dw_sel_bf16_ws_bytes": ctypes.c_longlong}
+             "lpd_edge_dw_sel_bf16_ws_bytes": ctypes.c_longlong, "lpd_road_planes_workspace_bytes": ctypes.c_longlong}
 
 _lib = None
 

@@ -123,11 +123,13 @@ class ScanStream:
     the batch just yielded).  Files are rows of `columns` values of `dtype`; a file that is empty, not a whole number of rows or
     longer than 2^20 rows is skipped.  Two pinned byte buffers and a copy stream, as SubmapStream; the buffers are sized from the
     byte sizes of the first batch's files and grow when a later batch needs more.  float64 rows are narrowed on the device
-    (lpd_f64_to_f32); float32 rows go to the kernel as they are, with ld = columns."""
+    (lpd_f64_to_f32); float32 rows go to the kernel as they are, with ld = columns.  clean: a submap.RoadRemoval -- range crop and
+    road removal on the device in front of the submaps (submap.make_submaps(clean=...); `last.cleaned` holds what it did)."""
 
     def __init__(self, filenames, batch_size, dataset_folder="", device=None, num_points=NUM_POINTS, dtype=np.float64, columns=3,
-                 normalize=True):
+                 normalize=True, clean=None):
         self.files = list(filenames)
+        self.clean = clean
         self.bs, self.folder, self.N = int(batch_size), dataset_folder, int(num_points)
         self.dtype, self.columns, self.normalize = np.dtype(dtype), int(columns), bool(normalize)
         if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or self.columns < 3:
@@ -209,24 +211,24 @@ class ScanStream:
             nxt, pos = self._stage(other, pos) if pos < len(self.files) else ([], pos)
             main.wait_event(self.ready[slot])
             rows = self.staged[slot][:sum(lengths) * self.row_bytes].view(tdtype).view(-1, self.columns)
-            self.last = submap.make_submaps(rows, lengths, self.N, self.normalize, check_finite=False)
+            self.last = submap.make_submaps(rows, lengths, self.N, self.normalize, check_finite=False, clean=self.clean)
             self.free[slot].record(main)
             yield self.last.x
             slot, lengths = other, nxt
 
 
 def get_latent_vectors_from_scans(model, filenames, batch_size, dataset_folder="", output_dim=256, num_points=NUM_POINTS,
-                                  dtype=np.float64, columns=3, normalize=True):
+                                  dtype=np.float64, columns=3, normalize=True, clean=None):
     """get_latent_vectors_from_files for raw scans of any length: eval mode, no_grad, batches of `batch_size` scans streamed from
     disk and made into submaps on the device (ScanStream), ragged tail, the previous train/eval mode restored afterwards;
-    -> numpy [n_ok, output_dim]."""
+    clean: a submap.RoadRemoval (range crop and road removal in front of the submaps) or None;  -> numpy [n_ok, output_dim]."""
     was_training = model.training
     model.eval()
     outs = []
     dev = next(model.parameters()).device
     try:
         with torch.no_grad():
-            for batch in ScanStream(filenames, batch_size, dataset_folder, dev, num_points, dtype, columns, normalize):
+            for batch in ScanStream(filenames, batch_size, dataset_folder, dev, num_points, dtype, columns, normalize, clean):
                 outs.append(model(batch).detach().cpu().numpy().reshape(batch.shape[0], -1))
     finally:
         model.train(was_training)

@@ -1311,6 +1311,79 @@ def radius_lists(qpos, dpos, radius, seg_off=None, skip_seg=None, self_item=None
     return off, idx, counts
 
 
+CLEAN_MAX_H, CLEAN_MAX_RANGE, CLEAN_CHUNK = 1024, 512.0, 1024      # csrc/lpd_clean_math.h
+
+
+class CleanParams(ctypes.Structure):
+    """LpdCleanParams of include/lpd_hip.h (submap.RoadRemoval validates the values and builds one)"""
+    _fields_ = [(n, ctypes.c_float) for n in ("r_min", "r_max", "z_lo", "z_hi", "seed_z_lo", "seed_z_hi", "tau", "min_det", "max_slope",
+                                              "clearance")] + \
+               [(n, ctypes.c_int32) for n in ("H", "min_inliers", "refine")] + \
+               [("seed_lo", ctypes.c_uint32), ("seed_hi", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+def _clean_head(what, points, offsets, B, max_len, params):
+    _req(points, "points")
+    _req(offsets, "offsets", torch.int32)
+    if points is None or offsets is None:
+        raise TypeError(f"{what}: points and offsets are tensors")
+    if not isinstance(params, CleanParams):
+        raise TypeError(f"{what}: params must be an ops.CleanParams (submap.RoadRemoval().c_params())")
+    B, max_len = int(B), int(max_len)
+    ld = _rows(points, "points")
+    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    if not 1 <= B <= 65535 or offsets.dim() != 1 or offsets.numel() != B + 1:
+        raise ValueError(f"{what}: offsets must hold B+1 entries with 1 <= B <= 65535, got B={B} and {tuple(offsets.shape)}")
+    if not 1 <= max_len <= SUBMAP_MAX_POINTS:
+        raise ValueError(f"{what}: max_len={max_len} outside 1 .. 2^20")
+    offsets = offsets.contiguous()
+    return (_ptr(points), ld, points.shape[0], _ptr(offsets), B, max_len, ctypes.byref(params)), B, max_len
+
+
+def road_planes(points, offsets, B, max_len, params):
+    """The road plane of every scan of a ragged batch (lpd_road_planes; definition in include/lpd_hip.h): points [rows, >=3] fp32 with
+    contiguous rows, offsets [B+1] int32 on the device, max_len = the host-known longest scan (it sizes the grid; a longer scan is not
+    read), params an ops.CleanParams -> (plane [B,4] = (a, b, c, 0), info [B,4] int32 = (n_live, h* or -1, S(h*), inliers of the final
+    plane)) on the device.  Nothing is read back; the workspace is allocated here."""
+    head, B, max_len = _clean_head("road_planes", points, offsets, B, max_len, params)
+    dev = points.device
+    lib = _lib.load()
+    plane = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(lib.lpd_road_planes_workspace_bytes(B, int(params.H))), 16),), dtype=torch.uint8, device=dev)
+    _call(f"road_planes[h={int(params.H)}]", lib.lpd_road_planes, *head, _ptr(plane), _ptr(info), _ptr(ws), _stream())
+    return plane, info
+
+
+def clean_scans(points, offsets, B, max_len, params, plane=None, info=None, want_mask=False):
+    """Crop, road removal and stable ragged compaction (lpd_clean_count, a torch.cumsum on the device, lpd_clean_fill; definition in
+    include/lpd_hip.h).  plane / info: what road_planes returned, or None (both) for the crop alone.
+    -> (out [rows,3] fp32: the kept rows of scan 0, then scan 1, ...; out_offsets [B+1] int32 on the device; mask [rows] uint8 or None).
+    Rows of `out` behind out_offsets[B] are not written.  Nothing is read back."""
+    head, B, max_len = _clean_head("clean_scans", points, offsets, B, max_len, params)
+    _req(plane, "plane")
+    _req(info, "info", torch.int32)
+    if (plane is None) != (info is None):
+        raise ValueError("clean_scans: plane and info go together")
+    if plane is not None:
+        if tuple(plane.shape) != (B, 4) or tuple(info.shape) != (B, 4):
+            raise ValueError(f"clean_scans: plane and info must be [B, 4] = ({B}, 4), got {tuple(plane.shape)} and {tuple(info.shape)}")
+        plane, info = plane.contiguous(), info.contiguous()
+    dev, rows = points.device, points.shape[0]
+    chunks = (max_len + CLEAN_CHUNK - 1) // CLEAN_CHUNK
+    counts = torch.empty((B * chunks,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    _call("clean_count", lib.lpd_clean_count, *head, _ptr(plane), _ptr(info), _ptr(counts), _stream())
+    off = torch.zeros((B * chunks + 1,), dtype=torch.int32, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int32, out=off[1:])      # at most `rows` < 2^31 in all
+    out = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    out_offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    mask = torch.zeros((rows,), dtype=torch.uint8, device=dev) if want_mask else None
+    _call("clean_fill", lib.lpd_clean_fill, *head, _ptr(plane), _ptr(info), _ptr(off), _ptr(out), _ptr(out_offsets), _ptr(mask), _stream())
+    return out, out_offsets, mask
+
+
 # ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------

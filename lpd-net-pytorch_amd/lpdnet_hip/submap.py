@@ -7,12 +7,16 @@ the number of occupied cells lands just under N, filled up to exactly N with raw
 
     sub = submap.make_submaps(scans)                     # list of [n_i, >=3] arrays / tensors  ->  sub.x [B,1,4096,3]
     sub = submap.make_submaps(points, lengths)           # one concatenated [sum n, >=3] tensor + host lengths (KITTI n x 4 rows as they are)
-    points, lengths = submap.filter_scans(points, lengths, mask)      # the caller's own range crop / ground removal, as a mask
+    sub = submap.make_submaps(scans, clean=submap.RoadRemoval(r_max=50.0))      # range crop + road removal on the device first
+    kept = submap.clean_scans(scans, clean=submap.RoadRemoval())                # that step alone: kept.points, kept.offsets, kept.plane
+    points, lengths = submap.filter_scans(points, lengths, mask)      # the escape hatch: any rule of the caller's own, as a mask
     model = submap.ScanInput(model)                      # ragged scans in, submaps made on the way
 
 Deterministic: the result does not depend on thread order, and the cell rows do not depend on the order of the raw points.  No CPU
 fallback: the work is done on the GPU (host arrays are uploaded to the current device).
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -25,11 +29,14 @@ NUM_POINTS = 4096
 class Submaps:
     """What make_submaps returns.  x [B,1,N,3] fp32, the model input; per cloud: level = the rung j* of the resolution ladder,
     cells = M rows that are cell averages (rows M .. N-1 are raw points), n_raw = points of the scan, center [B,3] and scale [B]
-    with row = x * scale + center (0 and 1 when normalize=False); counts [B,N] int32 = points per cell, 0 on fill rows, or None."""
-    __slots__ = ("x", "level", "cells", "n_raw", "center", "scale", "counts")
+    with row = x * scale + center (0 and 1 when normalize=False); counts [B,N] int32 = points per cell, 0 on fill rows, or None.
+    cleaned: the CleanedScans of make_submaps(clean=...), else None; n_raw then counts the rows that survived the cleaning, and a
+    scan that it emptied is the zero submap with level -1, cells 0, n_raw 0 (what lpd_make_submaps defines for an empty cloud)."""
+    __slots__ = ("x", "level", "cells", "n_raw", "center", "scale", "counts", "cleaned")
 
-    def __init__(self, x, info, xform, counts):
+    def __init__(self, x, info, xform, counts, cleaned=None):
         self.x = x
+        self.cleaned = cleaned
         self.level, self.cells, self.n_raw = info[:, 0], info[:, 1], info[:, 2]
         self.center, self.scale = xform[:, :3], xform[:, 3]
         self.counts = counts
@@ -89,27 +96,134 @@ def _device_rows(points, device):
     return points
 
 
-def make_submaps(scans_or_points, lengths=None, num_points=NUM_POINTS, normalize=True, check_finite=True, want_counts=False, device=None):
+class RoadRemoval:
+    """The parameters of the range crop and the road removal (include/lpd_hip.h states what each does), validated.  A row is live when
+    it is finite, r_min <= its range in plan view <= r_max (metres, at most 512) and z_lo <= z <= z_hi.  H plane hypotheses (0: crop
+    only, at most 1024), each through three live rows inside the seed band [seed_z_lo, seed_z_hi] (a sensor-height prior), at least
+    min_det (twice the triangle's plan area, m^2) apart and no steeper than max_slope (the norm of the gradient; 0.27 = 15 degrees);
+    the one with the most live rows within tau of it wins, needs min_inliers of them, is refined by one least-squares round over them
+    (refine), and every live row no higher than `clearance` above it is removed.  seed: 64 bits, the key of the draws."""
+    __slots__ = ("r_min", "r_max", "z_lo", "z_hi", "seed_z_lo", "seed_z_hi", "H", "tau", "min_det", "max_slope", "min_inliers", "refine",
+                 "clearance", "seed")
+
+    def __init__(self, r_min=0.0, r_max=512.0, z_lo=-math.inf, z_hi=math.inf, seed_z_lo=-math.inf, seed_z_hi=math.inf, H=256, tau=0.15,
+                 min_det=4.0, max_slope=0.27, min_inliers=16, refine=1, clearance=0.3, seed=0):
+        self.r_min, self.r_max, self.z_lo, self.z_hi = float(r_min), float(r_max), float(z_lo), float(z_hi)
+        self.seed_z_lo, self.seed_z_hi = float(seed_z_lo), float(seed_z_hi)
+        self.tau, self.min_det, self.max_slope, self.clearance = float(tau), float(min_det), float(max_slope), float(clearance)
+        for name in ("H", "min_inliers", "refine", "seed"):
+            v = locals()[name]
+            if isinstance(v, bool):
+                v = int(v)
+            if not isinstance(v, (int, np.integer)):
+                raise ValueError(f"RoadRemoval: {name}={v!r} must be an integer")
+            setattr(self, name, int(v))
+        if not 0.0 <= self.r_min <= self.r_max <= ops.CLEAN_MAX_RANGE:
+            raise ValueError(f"RoadRemoval: 0 <= r_min={self.r_min} <= r_max={self.r_max} <= {ops.CLEAN_MAX_RANGE:g} required")
+        for name in ("z_lo", "z_hi", "seed_z_lo", "seed_z_hi"):
+            if math.isnan(getattr(self, name)):
+                raise ValueError(f"RoadRemoval: {name} is NaN")
+        if self.z_lo > self.z_hi or self.seed_z_lo > self.seed_z_hi:
+            raise ValueError("RoadRemoval: a z band is empty (lo > hi)")
+        if not 0 <= self.H <= ops.CLEAN_MAX_H:
+            raise ValueError(f"RoadRemoval: H={self.H} outside 0 .. {ops.CLEAN_MAX_H}")
+        for name in ("tau", "min_det", "max_slope"):
+            v = getattr(self, name)
+            if not (0.0 <= v < math.inf):
+                raise ValueError(f"RoadRemoval: {name}={v} (finite, >= 0)")
+        if not math.isfinite(self.clearance):
+            raise ValueError(f"RoadRemoval: clearance={self.clearance} (finite)")
+        if not 0 <= self.min_inliers < 1 << 31:
+            raise ValueError(f"RoadRemoval: min_inliers={self.min_inliers} (>= 0)")
+        if self.refine not in (0, 1):
+            raise ValueError(f"RoadRemoval: refine={self.refine} (0 or 1)")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"RoadRemoval: seed={self.seed} outside 0 .. 2^64-1")
+
+    def c_params(self):
+        """-> ops.CleanParams, the C struct the entry points read (every float rounded to fp32)"""
+        return ops.CleanParams(self.r_min, self.r_max, self.z_lo, self.z_hi, self.seed_z_lo, self.seed_z_hi, self.tau, self.min_det,
+                               self.max_slope, self.clearance, self.H, self.min_inliers, self.refine, self.seed & 0xFFFFFFFF,
+                               self.seed >> 32, 0)
+
+    def __repr__(self):
+        return "RoadRemoval(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+
+class CleanedScans:
+    """What clean_scans returns, all on the device: points [rows,3] fp32 -- the kept rows of scan 0, then scan 1, ... (rows behind
+    offsets[-1] are not written); offsets [B+1] int32; plane [B,4] = (a, b, c, 0) with the road at z = a x + b y + c (zeros: no road
+    found, or H = 0); info [B,4] int32 = (live rows, the winning hypothesis or -1, its inliers, inliers of the final plane) -- (-1, -1,
+    0, 0) marks a scan that was not read; mask [rows] uint8 (1 = kept) or None.  lengths() is the one method that reads back."""
+    __slots__ = ("points", "offsets", "plane", "info", "mask")
+
+    def __init__(self, points, offsets, plane, info, mask):
+        self.points, self.offsets, self.plane, self.info, self.mask = points, offsets, plane, info, mask
+
+    def lengths(self):
+        """-> the kept rows per scan as a host list (waits for the device)"""
+        return torch.diff(self.offsets).cpu().tolist()
+
+
+def _offsets_of(lengths, device):
+    off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=off[1:])
+    if off[-1] >= 1 << 31:
+        raise ValueError(f"make_submaps: {int(off[-1])} rows in one batch exceed 2^31")
+    return torch.from_numpy(off.astype(np.int32)).to(device, non_blocking=True)
+
+
+def _clean_rows(rows, offsets, lengths, clean, want_mask):
+    if not isinstance(clean, RoadRemoval):
+        raise TypeError(f"clean must be a submap.RoadRemoval, got {type(clean).__name__}")
+    if len(lengths) > 65535:
+        raise ValueError(f"clean_scans: {len(lengths)} scans in one batch; at most 65535")
+    prm, B, longest = clean.c_params(), len(lengths), max(lengths)
+    plane, info = ops.road_planes(rows, offsets, B, longest, prm)
+    if clean.H > 0:
+        out, out_offsets, mask = ops.clean_scans(rows, offsets, B, longest, prm, plane, info, want_mask)
+    else:
+        out, out_offsets, mask = ops.clean_scans(rows, offsets, B, longest, prm, None, None, want_mask)
+    return CleanedScans(out, out_offsets, plane, info, mask)
+
+
+def clean_scans(scans_or_points, lengths=None, clean=RoadRemoval(), want_mask=False, device=None):
+    """Range crop and road removal of raw scans on the device (lpd_road_planes, lpd_clean_count, lpd_clean_fill; the definition is in
+    include/lpd_hip.h) -> CleanedScans.  Input as make_submaps takes it; NaN / inf rows are simply dropped.  want_mask: also return
+    the per-row keep mask (to carry intensity or labels along: extra[mask.bool()]).  Nothing is read back."""
+    points, lengths = _gather_input(scans_or_points, lengths)
+    with torch.no_grad():
+        rows = _device_rows(points, device)
+        return _clean_rows(rows, _offsets_of(lengths, rows.device), lengths, clean, want_mask)
+
+
+def make_submaps(scans_or_points, lengths=None, num_points=NUM_POINTS, normalize=True, check_finite=True, want_counts=False, device=None,
+                 clean=None):
     """Raw scans -> Submaps (x [B,1,num_points,3] on the GPU).  scans_or_points: a list of [n_i, >=3] tensors / arrays (columns
     behind the third are ignored), or ONE concatenated [sum n, >=3] tensor / array with host `lengths`.  Every scan has 1 .. 2^20
     points; 128 <= num_points <= 4096.  check_finite: reject NaN / inf coordinates (the definition is for finite input; on device
-    tensors the check waits for the device once)."""
+    tensors the check waits for the device once).  clean: a RoadRemoval -- the scans are cropped and their road is removed on the
+    device first (clean_scans; the result is `.cleaned`), the submaps are made from the rows that are left through the device-side
+    offsets: no wait for the device, and no check_finite pass (rows that are not finite are not live).  A scan that the cleaning
+    emptied gives the zero submap with level = -1, cells = 0, n_raw = 0."""
     N = int(num_points)
     if not ops.SUBMAP_MIN_N <= N <= ops.SUBMAP_MAX_N:
         raise ValueError(f"make_submaps: num_points={N} outside {ops.SUBMAP_MIN_N} .. {ops.SUBMAP_MAX_N}")
+    if clean is not None and not isinstance(clean, RoadRemoval):
+        raise TypeError(f"make_submaps: clean must be a submap.RoadRemoval or None, got {type(clean).__name__}")
     points, lengths = _gather_input(scans_or_points, lengths)
-    if check_finite and not bool(torch.isfinite(points[:, :3]).all()):
+    if clean is None and check_finite and not bool(torch.isfinite(points[:, :3]).all()):
         raise ValueError("make_submaps: a scan holds NaN or inf coordinates")
     with torch.no_grad():
         rows = _device_rows(points, device)
-        off = np.zeros(len(lengths) + 1, dtype=np.int64)
-        np.cumsum(lengths, out=off[1:])
-        if off[-1] >= 1 << 31:
-            raise ValueError(f"make_submaps: {int(off[-1])} rows in one batch exceed 2^31")
-        offsets = torch.from_numpy(off.astype(np.int32)).to(rows.device, non_blocking=True)
+        offsets = _offsets_of(lengths, rows.device)
         B = len(lengths)
+        cleaned = None
+        if clean is not None:
+            cleaned = _clean_rows(rows, offsets, lengths, clean, False)
+            rows, offsets = cleaned.points, cleaned.offsets
         out, info, xform, counts = ops._make_submaps(rows, offsets, B, N, normalize, want_counts, None)
-    return Submaps(out.view(B, 1, N, 3), info, xform, counts)
+    return Submaps(out.view(B, 1, N, 3), info, xform, counts, cleaned)
 
 
 def filter_scans(points, lengths, mask):
@@ -133,10 +247,13 @@ class ScanInput(nn.Module):
     current stream, in eval and in train mode (the submaps carry no gradient).  The wrapped model is `.module`, as with
     features.LocalFeatureInput and nn.DataParallel: harness.save_checkpoint / load_pretrained see the real model."""
 
-    def __init__(self, module, num_points=NUM_POINTS, normalize=True, check_finite=True):
+    def __init__(self, module, num_points=NUM_POINTS, normalize=True, check_finite=True, clean=None):
         super().__init__()
         self.module = module
         self.num_points, self.normalize, self.check_finite = int(num_points), bool(normalize), bool(check_finite)
+        if clean is not None and not isinstance(clean, RoadRemoval):
+            raise TypeError(f"ScanInput: clean must be a submap.RoadRemoval or None, got {type(clean).__name__}")
+        self.clean = clean      # range crop + road removal on the device in front of the submaps
 
     def forward(self, scans, lengths=None):
-        return self.module(make_submaps(scans, lengths, self.num_points, self.normalize, self.check_finite).x)
+        return self.module(make_submaps(scans, lengths, self.num_points, self.normalize, self.check_finite, clean=self.clean).x)
