@@ -827,20 +827,128 @@ __global__ __launch_bounds__(256) void knn7_bf16_kernel(const float* __restrict_
     *reinterpret_cast<knn_bf16x8*>(dst + (size_t)4 * 512) = e;
 }
 
-// grid (ceil(nt / 8), B), 256 threads: wave w of block x bounds query tiles 8 x + 2 w, + 1 against every candidate tile; two
-// waves per SIMD (one multiplies while the other finishes a tile: max over its candidates, bound, bf16 round-up, store).
+// grid (ceil(nt / 8), B, ranges), 256 threads: wave w of block x bounds query tiles 8 x + 2 w, + 1 against every candidate tile of
+// the block's range; two waves per SIMD.
+// The loop over candidate tiles is software-pipelined inside the wave.  Its first form ran every tile strictly in sequence -- five
+// MFMAs chained on ONE accumulator that both query tiles shared, the result latency, 16 v_med3, a ds_bpermute for the other
+// half-wave's maximum with its lgkmcnt(0), the bound, a branch around the store -- so no MFMA of a wave ever ran under its own
+// epilogue and the second wave of the SIMD was the only overlap there was: 95 us per launch at 32 x 4096 for ~36 us of matrix work.
+// Now there are two accumulator sets: a step issues the 2 x 5 MFMAs of tile T + 1 into the free set while the VALU reduces tile T
+// out of the other one (knn7_bound_step; __builtin_amdgcn_sched_group_barrier places a handful of VALU instructions behind every
+// MFMA).  The first tile is peeled (no predecessor), the last one is drained after the loop (knn7_bound_finish alone), and a range that
+// is no multiple of the ring ends in steps that are chosen tile by tile.  What else left the loop:
+//  * the cross-half maximum is ONE v_permlane32_swap for both query tiles, no LDS: swap(m0, m1) leaves (m0 of lanes 0..31, m0 of
+//    lanes 32..63) in the low half and (m1 low, m1 high) in the high half, so one more v_med3 gives half h the full maximum of
+//    query tile W0 + h -- and the selection of "its" tile for free;
+//  * half h therefore finishes and stores the bound of query tile W0 + h: one 2-byte store per candidate tile, not two, and
+//    no branch.  A wave whose second query tile does not exist (W0 + 1 == nt) computes tile W0 in both halves (same operands, same
+//    bits) and both halves store the same value to the same address;
+//  * the per-candidate-tile constants ncT = sqrt(xx_max) 1.0001 and cT = 2 (xx_max 2^-17 + E0) are computed once per block into
+//    LDS (sct): no sqrt and no LDS read in front of a tile's first MFMA;
+//  * vector instructions, because the pipelined loop is bound by the SIMD's vector ISSUE (an MFMA holds it for 8 of its 32 cycles,
+//    every other vector instruction for 4, and two waves share it): 47 per tile and wave as first pipelined (78.8 us), 35 now
+//    (72.4 us; the sequential kernel 94.6 .. 96.4 in the same sessions) -- the maximum of 16 in 12 instructions
+//    (knn7_bound_max16), the two doublings of the bound as fmaf(2, x, y), which rounds exactly where 2 x + y did, and buffer
+//    resources for the loads and the store (Knn7BoundCtx).
+// Timing-only builds of the 78.8 us form, same sessions: no loads in the loop 66 us, no store 69.5 us; dealing the blocks so that a
+// cloud's 16 stay on one XCD changed nothing (79).  One dword store per PAIR of candidate tiles (a lane trades one value with
+// its neighbour; two whole 128-byte lines per instruction) was bit-identical and no faster (0.772 of the parent against 0.765):
+// not kept.  Numbers: profiles/knn_bound_pipelined.txt.
+// The arithmetic is untouched -- the k-step order per accumulator, the (exact) maximum, the bound expression and its operation
+// order, the round-up -- so the table is bit-identical to the sequential form's (tests/test_knn_bound_gpu.py holds its output).
+// Only builtins touch accumulator values: inline asm reading an MFMA result is invisible to the hazard recogniser (lpd_edge.hip).
 // (Four query tiles per wave at one wave per SIMD, software-pipelined by hand, was slower: 133 us against 113.)
 constexpr int KNN7_BQT = 2;
+constexpr int KNN7_BRING = 4;     // candidate operand ring: register sets, requested KNN7_BRING - 1 tiles ahead of their MFMAs
+
+struct Knn7BoundCtx {
+    knn_bf16x8 qop[KNN7_BQT][4], ones;    // query operands of tiles W0, W0 + 1; the fifth k-step's operand of ones
+    float xqh, kqh, pinf;                 // |q|^2 and 7.9e-3 |q| of this lane's query (tile W0 + h); +inf behind an asm barrier
+    const float2* sct;                    // LDS: (ncT, cT) per candidate tile
+    // memory through buffer resources: an access is (resource, the lane's constant 32-bit offset, scalar offset of the tile), so a
+    // tile's addresses are scalar arithmetic.  With flat pointers every load and store of the loop cost one or two 64-bit vector
+    // adds -- and the vector issue slots beside the MFMAs are what this loop runs out of
+    __amdgpu_buffer_rsrc_t xres, ures;    // operand image / bound table of cloud b
+    unsigned xoff, uoff;                  // lane * 16; byte offset of table[W0 + h][0][col]
+    int nt;
+};
+
+// max as v_med3(a, b, +inf) with the +inf in a register the optimiser cannot see through: fmaxf on MFMA results costs three v_max
+// each (two canonicalising self-maxes)
+__device__ __forceinline__ float knn7_mx2(const Knn7BoundCtx& k, float a, float b) { return __builtin_amdgcn_fmed3f(a, b, k.pinf); }
+
+__device__ __forceinline__ void knn7_bound_load(const Knn7BoundCtx& k, int T, knn_bf16x8 (&c)[5])
+{
+    T = T < k.nt ? T : k.nt - 1;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) c[s] = __builtin_bit_cast(knn_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(k.xres, k.xoff, (unsigned)(T * 5 + s) * 1024u, 0));
+}
+
+__device__ __forceinline__ void knn7_bound_mma(const Knn7BoundCtx& k, const knn_bf16x8 (&c)[5], f32x16 (&a)[KNN7_BQT])
+{
+#pragma unroll
+    for (int i = 0; i < KNN7_BQT; ++i) {
+        f32x16 sa = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c[s], k.qop[i][s], sa, 0, 0, 0);
+        a[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c[4], k.ones, sa, 0, 0, 0);
+    }
+}
+
+// max of an accumulator's 16 values: the first level as v_med3 on the MFMA results, the rest as three-input maxima of those (fmaxf
+// of a v_med3 result needs no canonicalising self-max): 12 instructions, not 15.  The maximum is exact in any order.
+__device__ __forceinline__ float knn7_bound_max16(const Knn7BoundCtx& k, const f32x16& sa)
+{
+    float p[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = knn7_mx2(k, sa[2 * j], sa[2 * j + 1]);
+    const float a = fmaxf(fmaxf(p[0], p[1]), p[2]), b = fmaxf(fmaxf(p[3], p[4]), p[5]);
+    return fmaxf(fmaxf(a, b), fmaxf(p[6], p[7]));
+}
+
+// epilogue of candidate tile T from its two accumulators: max over the 32 candidates, bound, bf16 round-up, one store
+__device__ __forceinline__ void knn7_bound_finish(const Knn7BoundCtx& k, int T, const f32x16 (&a)[KNN7_BQT])
+{
+    const float m0 = knn7_bound_max16(k, a[0]), m1 = knn7_bound_max16(k, a[1]);
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(m0), __float_as_uint(m1), false, false);
+    const float m = knn7_mx2(k, __uint_as_float(r[0]), __uint_as_float(r[1]));      // all 32 candidates, query tile W0 + h
+    const float2 ct = k.sct[T];
+    // 2 m - xq + (2 (kq ncT) + cT): a doubling is exact, so each fused form rounds exactly where the separate operations did
+    float ub = fmaf(2.0f, m, -k.xqh) + fmaf(2.0f, k.kqh * ct.x, ct.y);
+    ub += fabsf(ub) * 9.5367431640625e-7f;                                        // the rounding of this expression itself
+    uint32_t bits = __float_as_uint(ub);
+    bits = (ub <= 0.0f) ? (bits >> 16) : 0x7f80u;                                 // truncation rounds a negative value up; else (or NaN) +inf
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bits, k.ures, k.uoff, (unsigned)T * 64u, 0);
+}
+
+// one pipelined step: the MFMAs of tile T + 1 (operands c) into an, under them the epilogue of tile T out of ap; LOAD: request tile
+// T + KNN7_BRING into cl, the set tile T has released
+template <bool LOAD>
+__device__ __forceinline__ void knn7_bound_step(const Knn7BoundCtx& k, int T, knn_bf16x8 (&cl)[5], const knn_bf16x8 (&c)[5],
+                                                f32x16 (&an)[KNN7_BQT], const f32x16 (&ap)[KNN7_BQT])
+{
+    if constexpr (LOAD) knn7_bound_load(k, T + KNN7_BRING, cl);
+    knn7_bound_mma(k, c, an);
+    knn7_bound_finish(k, T, ap);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);        // the tile's constants first: their use is ~40 instructions away
+#pragma unroll
+    for (int i = 0; i < 5 * KNN7_BQT; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);      // one MFMA (8 passes = 32 cycles of the matrix pipe) ...
+        __builtin_amdgcn_sched_group_barrier(0x2, 5, 0);      // ... and up to five VALU instructions of the epilogue in its shadow
+    }
+}
+
 __global__ __launch_bounds__(256, 2) void knn7_bound_kernel(const __bf16* __restrict__ xb, const float* __restrict__ xx,
                                                             const float* __restrict__ txmax, uint16_t* __restrict__ ubq, int N, int nt, int C,
                                                             int tchunk)
 {
-    constexpr int QT = KNN7_BQT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int QT = KNN7_BQT, RING = KNN7_BRING;
+    static_assert(QT == 2 && RING % 2 == 0, "two query tiles (one per half-wave at the store); accumulator sets alternate with the ring");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // uniform, and known to be: it reaches the buffer loads' scalar offsets
     const int h = lane >> 5, col = lane & 31;
     const int b = blockIdx.y;
     const int W0 = (blockIdx.x * 4 + wave) * QT;
-    const __bf16* xbb = xb + ((size_t)b * nt * 5 * 64 + lane) * 8;
     const float* txb = txmax + (size_t)b * nt;
     float smax = 0.f;
     for (int t = lane; t < nt; t += 64) smax = fmaxf(smax, txb[t]);
@@ -848,68 +956,61 @@ __global__ __launch_bounds__(256, 2) void knn7_bound_kernel(const __bf16* __rest
     for (int m = 32; m >= 1; m >>= 1) smax = fmaxf(smax, __shfl_xor(smax, m, 64));
     const float E0 = 8.0f * (float)(C + 8) * 1.1920929e-7f * smax + 1e-30f;       // the best-first kernel's slack (same expression)
 
-    knn_bf16x8 qop[QT][4], ones;
-    float xq[QT], kq[QT];
+    // per candidate tile, once: ncT = |c|_max (rounded up), cT = 2 (xx_max 2^-17 + E0)
+    __shared__ float2 sct[KNN7_PRE_MAXT];
+    for (int t = tid; t < nt; t += 256) {
+        const float tx = txb[t];
+        sct[t] = make_float2(sqrtf(tx) * 1.0001f, 2.0f * (tx * 7.62939453125e-6f + E0));
+    }
+    __syncthreads();
+    if (W0 >= nt) return;
+
+    Knn7BoundCtx k;
+    k.nt = nt;
+    k.sct = sct;
+    k.xres = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(const_cast<__bf16*>(xb)) + (size_t)b * nt * 5 * 1024, 0,
+                                               (unsigned)nt * 5 * 1024, 0x00020000);
+    k.xoff = lane * 16;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)((h == 0 && e < 2) ? 1.0f : 0.0f);
+    for (int e = 0; e < 8; ++e) k.ones[e] = (__bf16)((h == 0 && e < 2) ? 1.0f : 0.0f);
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
         const int Wq = min(W0 + i, nt - 1);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) qop[i][s] = *reinterpret_cast<const knn_bf16x8*>(xbb + ((size_t)Wq * 5 + s) * 512);
-        xq[i] = xx[(size_t)b * N + min(Wq * 32 + col, N - 1)];
-        kq[i] = (sqrtf(xq[i]) * 1.0001f + 1e-30f) * 7.9e-3f;                      // |q| (2 u + u^2 + accumulation), u = 2^-8
+        for (int s = 0; s < 4; ++s) k.qop[i][s] = __builtin_bit_cast(knn_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(k.xres, k.xoff, (unsigned)(Wq * 5 + s) * 1024u, 0));
     }
-    float pinf = INFINITY;
-    asm volatile("" : "+v"(pinf));
-    // max as v_med3(a, b, +inf) with the +inf in a register the optimiser cannot see through: fmaxf on MFMA results costs three
-    // v_max each (two canonicalising self-maxes)
-    auto mx2 = [&](float a_, float b_) { return __builtin_amdgcn_fmed3f(a_, b_, pinf); };
-    // candidate operands: a ring of RING register sets, requested RING - 1 tiles ahead (one tile ahead -- a copy at the end of
-    // the trip -- made every trip as long as an L2 round trip: 105 us, 1640 cycles per tile for 10 MFMAs)
-    constexpr int RING = 4;
-    knn_bf16x8 cop[RING][5];
-    auto load_c = [&](int T, knn_bf16x8 (&c)[5]) {
-        T = T < nt ? T : nt - 1;
-#pragma unroll
-        for (int s = 0; s < 5; ++s) c[s] = *reinterpret_cast<const knn_bf16x8*>(xbb + ((size_t)T * 5 + s) * 512);
-    };
-    __shared__ float stx[KNN7_PRE_MAXT];                 // xx_max of every tile (a global load per tile would be a dependent round trip)
-    for (int t = tid; t < nt; t += 256) stx[t] = txb[t];
-    __syncthreads();
-    if (W0 >= nt) return;
-    auto one_tile = [&](int T, const knn_bf16x8 (&c)[5]) {
-        const float tx = stx[T];
-        const float ncT = sqrtf(tx) * 1.0001f;
-        const float cT = 2.0f * (tx * 7.62939453125e-6f + E0);
-#pragma unroll
-        for (int i = 0; i < QT; ++i) {
-            f32x16 sa = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c[s], qop[i][s], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c[4], ones, sa, 0, 0, 0);
-            float m = mx2(mx2(mx2(sa[0], sa[1]), mx2(sa[2], sa[3])), mx2(mx2(sa[4], sa[5]), mx2(sa[6], sa[7])));
-            m = mx2(m, mx2(mx2(mx2(sa[8], sa[9]), mx2(sa[10], sa[11])), mx2(mx2(sa[12], sa[13]), mx2(sa[14], sa[15]))));
-            m = mx2(m, __shfl_xor(m, 32, 64));                                    // all 32 candidates of the tile
-            float ub = 2.0f * m - xq[i] + (2.0f * (kq[i] * ncT) + cT);
-            ub += fabsf(ub) * 9.5367431640625e-7f;                                // the rounding of this expression itself
-            uint32_t bits = __float_as_uint(ub);
-            bits = (ub <= 0.0f) ? (bits >> 16) : 0x7f80u;                         // truncation rounds a negative value up; else (or NaN) +inf
-            if (h == 0 && W0 + i < nt) ubq[(((size_t)b * nt + (W0 + i)) * nt + T) * 32 + col] = (uint16_t)bits;
-        }
-    };
+    const int Wh = min(W0 + h, nt - 1);                                           // this half's query tile (W0 again where W0 + 1 == nt)
+    k.xqh = xx[(size_t)b * N + min(Wh * 32 + col, N - 1)];
+    k.kqh = (sqrtf(k.xqh) * 1.0001f + 1e-30f) * 7.9e-3f;                          // |q| (2 u + u^2 + accumulation), u = 2^-8
+    k.ures = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(ubq) + (size_t)b * nt * nt * 64, 0, (unsigned)nt * nt * 64, 0x00020000);
+    k.uoff = ((unsigned)Wh * nt * 32 + col) * 2;                                  // < nt^2 64 <= 16 MiB
+    k.pinf = INFINITY;
+    asm volatile("" : "+v"(k.pinf));
+
     // blockIdx.z: this block's range of candidate tiles (tchunk, a multiple of RING).  One range for large batches; a small batch
     // (one cloud = 16 blocks of a 256-CU chip, each walking all 128 candidate tiles: 85 us of latency) is cut into up to 8 ranges
     const int tbeg = blockIdx.z * tchunk, tend = min(nt, tbeg + tchunk);
+    if (tbeg >= tend) return;
+    // candidate operands: a ring of RING register sets, requested RING - 1 tiles ahead (one tile ahead -- a copy at the end of
+    // the trip -- made every trip as long as an L2 round trip: 105 us, 1640 cycles per tile for 10 MFMAs)
+    knn_bf16x8 cop[RING][5];
+    f32x16 acc[2][QT];
 #pragma unroll
-    for (int d = 0; d < RING - 1; ++d) load_c(tbeg + d, cop[d]);
-    for (int T0 = tbeg; T0 < tend; T0 += RING) {
+    for (int d = 0; d < RING; ++d) knn7_bound_load(k, tbeg + d, cop[d]);
+    knn7_bound_mma(k, cop[0], acc[0]);                                            // peeled: the first tile has no predecessor
+    int T0 = tbeg;                                                                // tile T0 sits in acc[0], tiles T0 + 1 .. + 3 in cop[1 .. 3]
+    for (; T0 + RING < tend; T0 += RING) {
 #pragma unroll
-        for (int d = 0; d < RING; ++d) {
-            load_c(T0 + d + RING - 1, cop[(d + RING - 1) % RING]);      // the set tile T0 + d - 1 has just released
-            if (T0 + d < tend) one_tile(T0 + d, cop[d]);
-        }
+        for (int d = 0; d < RING; ++d) knn7_bound_step<true>(k, T0 + d, cop[d], cop[(d + 1) % RING], acc[(d + 1) & 1], acc[d & 1]);
     }
+    // the last 1 .. RING tiles of the range: pipelined while there is a next tile, then the drain
+    static_assert(RING == 4, "the tail below is written out for four sets");
+    const int left = tend - T0;                                                   // 1 .. RING
+    if (left > 1) knn7_bound_step<false>(k, T0, cop[0], cop[1], acc[1], acc[0]);
+    if (left > 2) knn7_bound_step<false>(k, T0 + 1, cop[1], cop[2], acc[0], acc[1]);
+    if (left > 3) knn7_bound_step<false>(k, T0 + 2, cop[2], cop[3], acc[1], acc[0]);
+    if (left & 1) knn7_bound_finish(k, tend - 1, acc[0]);
+    else knn7_bound_finish(k, tend - 1, acc[1]);
 }
 
 // tile statistics: centroid (packed operand layout), |c|^2, radius (inflated), max |x|^2.  One wave per tile.
