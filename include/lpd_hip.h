@@ -90,7 +90,18 @@ int lpd_knn_pm(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* i
  * [B*nt] each; nt = ceil(N / 32), cp = 2 for C <= 4 else 32; NULL when the best-first search will not run).  "Prepared" means
  * all of these. */
 #define LPD_KNN_PM_PREPARED 256
+/* (C = 3, N % 32 == 0: lpd_morton_sort_knn prepares the workspace of the xyz search the same way.) */
 int lpd_knn_pm_layout(int B, int C, int N, int k, float* ws, float** xx, float** xp, void** xb, float** tiles);
+/* Default path (the xyz graph of the LPD-Net eval forward): lpd_knn_pm whose lists also leave as the blocked uint16 copy that
+ * lpd_pack_idx16 makes (k = 20, N % 32 == 0; idx16 [B*N][20] uint16, 16-byte aligned), bit for bit.  Where lpd_knn_pm16_fused(C, N, k,
+ * impl) is 1 the search's final merge writes the 1280-byte blocks itself -- a wave's 32 queries are exactly one block -- and idx may be
+ * NULL (no int32 lists are written); elsewhere (the ascending scan, the branchy / statistics variants, LPD_DEBUG=knn-pack16=0) idx is
+ * required and lpd_pack_idx16 runs behind the search as a launch of its own. */
+int lpd_knn_pm16_fused(int C, int N, int k, int impl);
+/* Infrastructure: the byte offset of neighbour s (0 .. 19) of row m inside the blocked uint16 lists (the address arithmetic of the
+ * search's packed store; host only, -1 for arguments out of range). */
+long long lpd_idx16_offset(long long m, int s);
+int lpd_knn_pm16(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* idx, uint16_t* idx16, float* ws, int impl, void* stream);
 
 /*
  * The layers in front of the feature-space kNN of LPD-Net in one launch (util/lpdnet_model.py:231-232, no T-Nets):
@@ -407,6 +418,14 @@ int lpd_f64_to_f32(const double* in, float* out, long long n, void* stream);
  * invariant to point order; sorting makes the neighbour gathers of the aggregation kernels cache-local.
  * xyz/out [B][N][3] (out != xyz), perm [B][N] int32 or NULL.  N <= 16384. */
 int lpd_morton_sort(const float* xyz, float* out, int32_t* perm, int B, int N, void* stream);
+/* Default path (the head of the LPD-Net eval forward): the same sort, which also leaves what the xyz search wants in its workspace
+ * knn_ws (lpd_knn_workspace_floats(B, 3, N, k) floats, laid out by lpd_knn_pm_layout(B, 3, N, k, ...)): squared norms, the packed
+ * operand image and the statistics of the 32-point tiles of the SORTED cloud, bit for bit what lpd_knn_pm on the sorted rows writes
+ * there in its prep and tile-statistics launches.  lpd_knn_pm(NULL, 3, B, 3, N, k, idx, knn_ws, LPD_KNN_PM_PREPARED, stream) then
+ * builds the graph without those launches.  lpd_morton_sort_knn_applies(N, k): N % 32 == 0, 64 <= N <= 16384 and the best-first
+ * search on these sizes (LPD_DEBUG=sort-knn=0: never); LPD_ERR_UNSUPPORTED elsewhere. */
+int lpd_morton_sort_knn_applies(int N, int k);
+int lpd_morton_sort_knn(const float* xyz, float* out, int32_t* perm, int B, int N, int k, float* knn_ws, void* stream);
 
 /*
  * Local point-distribution features from sorted neighbour lists (csrc/lpd_feat.hip): the handcrafted per-point columns that the

@@ -1391,7 +1391,25 @@ template <> __device__ __forceinline__ void knn_merge_batch<16>(unsigned (&kh)[2
     KNN_PLACE(0, 1, 2, 3, 16, 17, 18, 19, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
 }
 
-// WAVES: waves per workgroup.  A workgroup's LDS and wave slots stay taken until its slowest wave is done and the tile
+// The finished list of one query, k = 20, as lpd_pack_idx16 lays it out (csrc/lpd_edge.hip, pack_idx16_kernel): the 32 queries of a
+// wave are one 1280-byte block [32 x 16 B: neighbours 0-7 | 32 x 16 B: 8-15 | 32 x 8 B: 16-19], values 16 * index as uint16.  m0: the
+// global row of the wave's first query (a multiple of 32: whole tiles, N % 32 == 0); p: the query's place in the wave.
+__host__ __device__ inline size_t knn_idx16_offset(size_t m, int s)      // byte offset of neighbour s (0 .. 19) of row m
+{
+    const size_t blk = (m >> 5) * 1280, p = m & 31;
+    return blk + (s < 16 ? (size_t)(s >> 3) * 512 + p * 16 + (size_t)(s & 7) * 2 : 1024 + p * 8 + (size_t)(s - 16) * 2);
+}
+__device__ __forceinline__ void knn7_store_idx16(uint16_t* __restrict__ idx16, size_t m0, int p, const int (&o)[20])
+{
+    unsigned char* base = reinterpret_cast<unsigned char*>(idx16);
+    const size_t m = m0 + (size_t)p;
+    auto pk = [](int a, int b) { return (uint32_t)((a << 4) & 0xffff) | ((uint32_t)b << 20); };
+    *reinterpret_cast<uint4*>(base + knn_idx16_offset(m, 0)) = make_uint4(pk(o[0], o[1]), pk(o[2], o[3]), pk(o[4], o[5]), pk(o[6], o[7]));
+    *reinterpret_cast<uint4*>(base + knn_idx16_offset(m, 8)) = make_uint4(pk(o[8], o[9]), pk(o[10], o[11]), pk(o[12], o[13]), pk(o[14], o[15]));
+    *reinterpret_cast<uint2*>(base + knn_idx16_offset(m, 16)) = make_uint2(pk(o[16], o[17]), pk(o[18], o[19]));
+}
+
+// WAVES: waves per workgroup. A workgroup's LDS and wave slots stay taken until its slowest wave is done and the tile
 // counts of neighbouring waves differ (C = 64: mean 51, p90 69, max 89 tiles): single-wave workgroups at C = 64
 // (638 -> 607 us), four waves at C = 3 (shorter waves; the larger groups launch faster: 278 vs 287 us).
 // SPLIT (round 5): SPLIT waves of one workgroup share ONE query tile W and divide its walk among them -- the visited tiles in walk
@@ -1411,7 +1429,7 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
                                                              const float* __restrict__ rad, const float* __restrict__ txmax,
                                                              int32_t* __restrict__ idx, const int32_t* __restrict__ order,
                                                              int N, int k, int nt, int C, int blocks_per_cloud, int dbg,
-                                                             const uint16_t* __restrict__ ubq)
+                                                             const uint16_t* __restrict__ ubq, uint16_t* __restrict__ idx16)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem7[];
     if constexpr (FULLT) dbg = 0;      // diagnostics (statistics, phase clocks) live in the branchy variant only: they cost ~17 registers
@@ -1949,7 +1967,7 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
                 pos[w2] = 0;
             }
             int32_t* out = idx + ((size_t)b * N + q) * k;
-            for (int s = 0; s < k; ++s) {
+            auto next = [&]() {                   // the best head of the SPLIT lists; its list moves on
                 int bw = 0;
                 float bvv = hv[0];
                 int bii = hi[0];
@@ -1960,7 +1978,6 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
                     bvv = better ? hv[w2] : bvv;
                     bii = better ? hi[w2] : bii;
                 }
-                out[s] = bii;
 #pragma unroll
                 for (int w2 = 0; w2 < SPLIT; ++w2) {
                     if (bw == w2) {
@@ -1971,7 +1988,20 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
                         hi[w2] = more ? __float_as_int(mbase[w2 * WSTRIDE + IOFF + pp]) : 0x7fffffff;
                     }
                 }
-            }
+                return bii;
+            };
+            static_assert(KMAX == 20, "the packed block holds lists of 20");
+            if (idx16) {      // k == 20: the list in registers, out as the query's three pieces of the packed block (int32 copy optional)
+                int o[KMAX];
+#pragma unroll
+                for (int s = 0; s < KMAX; ++s) o[s] = next();
+                knn7_store_idx16(idx16, (size_t)b * N + q0, col, o);
+                if (idx) {
+#pragma unroll
+                    for (int s = 0; s < KMAX; ++s) out[s] = o[s];
+                }
+            } else
+                for (int s = 0; s < k; ++s) out[s] = next();
         }
         return;
     }
@@ -1989,6 +2019,29 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
         const int* bi = mi + (lane + 32) * KMAX;
         int pa = 0, pb = 0;
         int32_t* out = idx + ((size_t)b * N + q) * k;
+        if constexpr (KMAX == 20) {
+            if (idx16) {      // k == 20 (pa + pb = s < KMAX: neither half-list runs out): the same merge with the list in registers,
+                              // out as the query's three pieces of the packed block; the int32 copy is optional
+                int o[KMAX];
+#pragma unroll
+                for (int s = 0; s < KMAX; ++s) {
+                    const float va = av[pa], vb2 = bv[pb];
+                    const int ia = ai[pa], ib = bi[pb];
+                    const bool take_a = (va > vb2) || (va == vb2 && ia < ib);
+                    o[s] = take_a ? ia : ib;
+                    pa += take_a ? 1 : 0;
+                    pb += take_a ? 0 : 1;
+                    pa = min(pa, KMAX - 1);       // (the last step may move one past the end; nothing reads it)
+                    pb = min(pb, KMAX - 1);
+                }
+                knn7_store_idx16(idx16, (size_t)b * N + q0, col, o);
+                if (idx) {
+#pragma unroll
+                    for (int s = 0; s < KMAX; ++s) out[s] = o[s];
+                }
+                return;
+            }
+        }
         for (int s = 0; s < k; ++s) {
             bool take_a;
             if (pa >= KMAX) take_a = false;
@@ -2034,6 +2087,19 @@ inline size_t knn7_extra_floats(int B, int N, int CP)
     return n;
 }
 
+// LPD_DEBUG=knn-fullt=0: the branchy tile body for every N
+inline bool knn7_branchy()
+{
+    static const bool branchy = lpd_debug("knn-fullt", 1) == 0;
+    return branchy;
+}
+// does the best-first search write the packed uint16 lists from its final merge (k = 20, whole tiles, the branch-free kernels)?
+// LPD_DEBUG=knn-pack16=0: never (the separate lpd_pack_idx16 launch)
+inline bool knn7_packs16(int N, int k, int dbg)
+{
+    static const bool on = lpd_debug("knn-pack16", 1) != 0;
+    return on && k == 20 && N % 32 == 0 && !knn7_branchy() && !dbg;
+}
 // the low-precision bound pass (LPD_DEBUG=knn-pre=0: centroid / radius bounds) and where its bf16 operand image lives in the workspace
 inline bool knn7_tight()
 {
@@ -2051,7 +2117,7 @@ inline __bf16* knn7_xb_of(const float* xx, int B, int N)      // 64 channels (CP
 
 template <int CP, int KMAX, bool ONFLY>
 int knn7_launch(const float* x, const float* xx, int32_t* idx, int B, int C, int N, int k, hipStream_t stream, int dbg = 0, bool xb_ready = false,
-                bool stats_ready = false)
+                bool stats_ready = false, uint16_t* idx16 = nullptr)
 {
     using L = Knn7Cfg<CP, KMAX, ONFLY>;
     static_assert(L::WAVE >= L::MERGE, "merge region must fit the wave's LDS region");
@@ -2086,7 +2152,9 @@ int knn7_launch(const float* x, const float* xx, int32_t* idx, int B, int C, int
             LPD_CHECK_LAUNCH("lpd_knn(low-precision bounds)");
         }
     }
-    static const bool branchy = lpd_debug("knn-fullt", 1) == 0;     // 0: the branchy tile body for every N
+    const bool branchy = knn7_branchy();
+    // the final merge writes lpd_pack_idx16's blocks itself (knn7_packs16 has said so to the caller; idx may then be null)
+    uint16_t* const out16 = (idx16 && knn7_packs16(N, k, dbg)) ? idx16 : nullptr;
     // Small batches: KNN7_SPLIT waves per query tile (see knn7_kernel).  LPD_DEBUG=knn-split=0 never, =1 always (where it is built); default:
     // while the split grid fits the wave slots of the chip (256 CUs x 4 SIMDs x waves per SIMD).
     constexpr int KNN7_SPLIT = 4;
@@ -2119,7 +2187,7 @@ int knn7_launch(const float* x, const float* xx, int32_t* idx, int B, int C, int
             (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(kern, dim3(bpc * B), dim3(threads), lds, stream, (const float*)xp, xx, (const float*)cenp,
                                (const float*)cnorm, (const float*)rad, (const float*)txmax, idx, (const int32_t*)(use_order ? order : nullptr),
-                               N, k, nt, C, bpc, dbg, (const uint16_t*)ubq);
+                               N, k, nt, C, bpc, dbg, (const uint16_t*)ubq, KMAX == 20 ? out16 : (uint16_t*)nullptr);
         };
         if constexpr (split_built) {
             if (split) {
@@ -2142,12 +2210,13 @@ int knn7_launch(const float* x, const float* xx, int32_t* idx, int B, int C, int
 constexpr int KNN7_MAXN = 65536;
 inline bool knn7_applies(int C, int N, int k) { return C <= 64 && k <= 64 && N <= KNN7_MAXN; }
 inline int knn7_dispatch(const float* x, const float* xx, int32_t* idx, int B, int C, int N, int k, hipStream_t stream, int dbg, bool xb_ready = false,
-                         bool stats_ready = false)
+                         bool stats_ready = false, uint16_t* idx16 = nullptr)
 {
     const bool small = k <= 20 && N <= KNN7_MAXT * 32;
-    if (C <= 4) return k <= 20 ? knn7_launch<2, 20, true>(x, xx, idx, B, C, N, k, stream, dbg) : knn7_launch<2, 64, true>(x, xx, idx, B, C, N, k, stream, dbg);
-    if (small) return knn7_launch<32, 20, false>(x, xx, idx, B, C, N, k, stream, dbg, xb_ready, stats_ready);
-    return k <= 20 ? knn7_launch<32, 20, true>(x, xx, idx, B, C, N, k, stream, dbg, xb_ready, stats_ready)
+    if (C <= 4) return k <= 20 ? knn7_launch<2, 20, true>(x, xx, idx, B, C, N, k, stream, dbg, false, stats_ready, idx16)
+                               : knn7_launch<2, 64, true>(x, xx, idx, B, C, N, k, stream, dbg, false, stats_ready);
+    if (small) return knn7_launch<32, 20, false>(x, xx, idx, B, C, N, k, stream, dbg, xb_ready, stats_ready, idx16);
+    return k <= 20 ? knn7_launch<32, 20, true>(x, xx, idx, B, C, N, k, stream, dbg, xb_ready, stats_ready, idx16)
                    : knn7_launch<32, 64, true>(x, xx, idx, B, C, N, k, stream, dbg, xb_ready, stats_ready);
 }
 
@@ -2264,23 +2333,61 @@ extern "C" int lpd_knn_pm_layout(int B, int C, int N, int k, float* ws, float** 
 
 // Point-major entry: x_pm [B*N][ld] rows (C <= 64 channels used).  Same results as lpd_knn on the transposed input; skips
 // the channel-major round trip (transpose + pack) that the pipeline would otherwise pay for each graph.
+namespace {
+// do these sizes take the search whose final merge writes lpd_pack_idx16's blocks (then the int32 lists are optional)?
+inline bool knn_pm_packs16(int C, int N, int k, int impl)
+{
+    impl &= ~LPD_KNN_PM_PREPARED;
+    return ((impl == 0 && KNN7_DEFAULT) || impl == 6) && C <= 64 && knn7_applies(C, N, k) && knn7_packs16(N, k, 0);
+}
+int knn_pm_run(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* idx, uint16_t* idx16, float* ws, int impl, void* stream_);
+}  // namespace
+
 extern "C" int lpd_knn_pm(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* idx, float* ws, int impl, void* stream_)
 {
+    LPD_CHECK_ARG(idx, "lpd_knn_pm: null pointer");
+    return knn_pm_run(x_pm, ld, B, C, N, k, idx, nullptr, ws, impl, stream_);
+}
+
+extern "C" int lpd_knn_pm16_fused(int C, int N, int k, int impl) { return knn_pm_packs16(C, N, k, impl) ? 1 : 0; }
+
+extern "C" long long lpd_idx16_offset(long long m, int s)
+{
+    if (m < 0 || s < 0 || s >= 20) return -1;
+    return (long long)knn_idx16_offset((size_t)m, s);
+}
+
+extern "C" int lpd_knn_pm16(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* idx, uint16_t* idx16, float* ws, int impl,
+                            void* stream_)
+{
+    LPD_CHECK_ARG(idx16 && ((uintptr_t)idx16 & 15) == 0, "lpd_knn_pm16: idx16 must be a 16-byte aligned pointer");
+    LPD_CHECK_ARG(k == 20 && N > 0 && N % 32 == 0, "lpd_knn_pm16: the packed lists are built for k = 20 and whole 32-point tiles (k=%d N=%d)", k, N);
+    const bool fused = knn_pm_packs16(C, N, k, impl);
+    LPD_CHECK_ARG(idx || fused, "lpd_knn_pm16: these sizes pack in a launch of their own and need the int32 lists (lpd_knn_pm16_fused)");
+    LPD_CHECK_ARG(!idx || ((uintptr_t)idx & 15) == 0, "lpd_knn_pm16: idx must be 16-byte aligned");
+    const int rc = knn_pm_run(x_pm, ld, B, C, N, k, idx, fused ? idx16 : nullptr, ws, impl, stream_);
+    if (rc != LPD_OK || fused) return rc;
+    return lpd_pack_idx16(idx, idx16, (long long)B * N, k, stream_);
+}
+
+namespace {
+int knn_pm_run(const float* x_pm, int ld, int B, int C, int N, int k, int32_t* idx, uint16_t* idx16, float* ws, int impl, void* stream_)
+{
     hipStream_t stream = (hipStream_t)stream_;
-    LPD_CHECK_ARG((x_pm || (impl & LPD_KNN_PM_PREPARED)) && idx && ws, "lpd_knn_pm: null pointer");
+    LPD_CHECK_ARG((x_pm || (impl & LPD_KNN_PM_PREPARED)) && (idx || idx16) && ws, "lpd_knn_pm: null pointer");
     LPD_CHECK_ARG(B > 0 && C > 0 && N > 0 && ld >= C, "lpd_knn_pm: bad dims B=%d C=%d N=%d ld=%d", B, C, N, ld);
     LPD_CHECK_ARG(k > 0 && k <= N, "lpd_knn_pm: need 0 < k <= N (k=%d N=%d)", k, N);
     LPD_CHECK_ARG(C <= 64 && k <= 64, "lpd_knn_pm: built for C <= 64, k <= 64 (got C=%d k=%d); use lpd_knn on the channel-major tensor", C, k);
     LPD_CHECK_ARG(C <= 4 || (impl & LPD_KNN_PM_PREPARED) || ((uintptr_t)x_pm & 15) == 0, "lpd_knn_pm: x_pm must be 16-byte aligned");
     const long long M = (long long)B * N;
     float* xp = ws + M;
-    const bool prepped = (impl & LPD_KNN_PM_PREPARED) != 0;     // the operands are in ws already (lpd_lpdnet_front)
+    const bool prepped = (impl & LPD_KNN_PM_PREPARED) != 0;     // the operands are in ws already (lpd_lpdnet_front, lpd_morton_sort_knn)
     impl &= ~LPD_KNN_PM_PREPARED;
     LPD_CHECK_ARG(impl == 0 || impl == 4 || impl == 5 || impl == 6, "lpd_knn_pm: impl=%d (0 product; 4 / 6 force the ascending / best-first kernel; 5 statistics)", impl);
     const bool best_first = ((impl == 0 && KNN7_DEFAULT) || (impl == 5 || impl == 6)) && knn7_applies(C, N, k);
     // the bf16 operand image of the low-precision bound pass is written with the operands when that pass will run
     const bool xb_ready = knn_pm_wants_xb(C, N, k, impl) && (prepped || ld % 4 == 0);
-    LPD_CHECK_ARG(!prepped || C == 64, "lpd_knn_pm: prepared operands are a 64-channel affair (C=%d)", C);
+    LPD_CHECK_ARG(!prepped || C == 64 || (C == 3 && N % 32 == 0), "lpd_knn_pm: prepared operands come with 64 channels, or 3 and whole tiles (C=%d N=%d)", C, N);
     if (prepped) { /* nothing to do */ }
     else if (C <= 4) hipLaunchKernelGGL(knn_prep_pm_kernel<2>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, x_pm, ld, ws, xp, C, M);
     else if (C == 64 && ld % 4 == 0) {      // four lanes per point
@@ -2288,7 +2395,8 @@ extern "C" int lpd_knn_pm(const float* x_pm, int ld, int B, int C, int N, int k,
                            xb_ready ? knn7_xb_of(ws, B, N) : (__bf16*)nullptr, M, N, (N + 31) / 32);
     } else hipLaunchKernelGGL(knn_prep_pm_kernel<32>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, x_pm, ld, ws, xp, C, M);
     LPD_CHECK_LAUNCH("lpd_knn_pm(prep)");
-    if (best_first) return knn7_dispatch(nullptr, ws, idx, B, C, N, k, stream, impl == 5, xb_ready, prepped);
+    if (best_first) return knn7_dispatch(nullptr, ws, idx, B, C, N, k, stream, impl == 5, xb_ready, prepped, idx16);
     if (C <= 4) return knn3_dispatch_k<2>(nullptr, ws, idx, B, C, N, k, stream);
     return knn3_dispatch_k<32>(nullptr, ws, idx, B, C, N, k, stream);
 }
+}  // namespace

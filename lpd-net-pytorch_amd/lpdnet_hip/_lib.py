@@ -62,6 +62,9 @@ SIGNATURES = {
     "lpd_knn_pm_layout": [_c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
     "lpd_lpdnet_front": [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p],
     "lpd_knn_pm": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_int, _c_p],
+    "lpd_knn_pm16_fused": [_c_int, _c_int, _c_int, _c_int],
+    "lpd_idx16_offset": [_c_ll, _c_int],
+    "lpd_knn_pm16": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_p],
     "lpd_knn_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
     "lpd_edge_gather_max": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
                             _c_int, _c_int, _c_f, _c_p],
@@ -91,6 +94,8 @@ SIGNATURES = {
     "lpd_mul": [_c_p, _c_p, _c_p, _c_ll, _c_p],
     "lpd_gating": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p],
     "lpd_morton_sort": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p],
+    "lpd_morton_sort_knn_applies": [_c_int, _c_int],
+    "lpd_morton_sort_knn": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p],
     "lpd_local_features": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int, ctypes.c_uint, _c_int, _c_p, _c_int, _c_p, _c_p],
     "lpd_make_submaps": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
     "lpd_sample_items": [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_ulonglong, _c_p, _c_p,
@@ -165,7 +170,7 @@ SIGNATURES = {
     "lpd_metric_loss": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_p, _c_ll, _c_ll, _c_p, _c_ll, _c_int, _c_int, _c_int,
                         _c_int, _c_f, _c_f, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
 }
-_RESTYPES = {"lpd_last_error": ctypes.c_char_p, "lpd_stat_ws_bytes": ctypes.c_longlong, "lpd_knn_workspace_floats": ctypes.c_longlong,
+_RESTYPES = {"lpd_last_error": ctypes.c_char_p, "lpd_stat_ws_bytes": ctypes.c_longlong, "lpd_knn_workspace_floats": ctypes.c_longlong, "lpd_idx16_offset": ctypes.c_longlong,
              "lpd_gemm_prep_b_bytes": ctypes.c_longlong, "lpd_gemm_tn_bf16_ws_floats": ctypes.c_longlong, "lpd_gemm_tn_ws_floats": ctypes.c_longlong,
              "lpd_gemm_tn_act_ws_floats": ctypes.c_longlong,
              "lpd_edge_dw_sel_bf16_ws_bytes": ctypes.c_longlong, "lpd_road_planes_workspace_bytes": ctypes.c_longlong}

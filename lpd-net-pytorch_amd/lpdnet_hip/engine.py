@@ -67,6 +67,15 @@ def reorder_points(x, reorder=True):
     return x
 
 
+def reorder_points_knn(x, reorder, k):
+    """reorder_points for a trunk whose xyz graph is built on the reordered cloud: -> (x, ws).  ws: the kNN workspace of that search with
+    its operands and tile statistics already in place (ops.morton_sort_knn; ops.knn_prepared(ws, B, N, k, C=3) builds the graph), or None
+    where the sort does not run or does not prepare it -- the search then prepares its own."""
+    if reorder and _morton_order() and 64 <= x.shape[2] <= MORTON_MAX_POINTS and ops.morton_sort_knn_applies(x.shape[2], k):
+        return ops.morton_sort_knn(x, k)
+    return reorder_points(x, reorder), None
+
+
 # ------------------------------------------------------------------------------------------------
 # cached derived parameters
 # ------------------------------------------------------------------------------------------------
@@ -480,14 +489,14 @@ def lpdnet_features_eval(net, x, reorder=True, assign=None):
     runs on lpd_gemm_p8, its assignment product x . cluster_weights (PointNetVlad.py:48) is computed in the same launch and the
     partial planes are returned as a fourth value (None otherwise) for netvlad_eval(logit_parts=...)."""
     mfea = getattr(net, "use_mFea", False)
-    x = _check_input(x, 8) if mfea else reorder_points(_check_input(x), reorder)
+    x, xyz_ws = (_check_input(x, 8), None) if mfea else reorder_points_knn(_check_input(x), reorder, net.k)
     B, N = x.shape[0], x.shape[2]
     act = ops.ACT_RELU if net.use_relu else ops.ACT_LEAKY
     side_ok = PANEL_LAYOUT and N % 128 == 0 and _resident_shape(net.k, N, B * N, act)
     # (round 6) with x1 written by the fused edge MLP the second stream holds the xyz kNN and the DG1 projection only -- no HBM-bound
     # K-agg beside the edge MLP any more -- and pays at every batch size: 32 clouds 1.91 -> 1.84 ms on three boxes
     light = side_ok and _x1_rides(net, B * N, N)
-    out = _lpdnet_features_eval_body(net, x, mfea, side_ok and _side_mode(x.device, B * N, light), assign)
+    out = _lpdnet_features_eval_body(net, x, mfea, side_ok and _side_mode(x.device, B * N, light), assign, xyz_ws)
     return out if assign is not None else out[:3]
 
 
@@ -501,7 +510,7 @@ def _x1_rides(net, M, N):
     return bool(net.k == 20 and N <= 4096 and _split_planes(net, N) and ops.edge_mlp_x1_applies(M, N, 128, net.convDG2[0].weight.shape[0]))
 
 
-def _lpdnet_features_eval_body(net, x, mfea, use_side, assign=None):
+def _lpdnet_features_eval_body(net, x, mfea, use_side, assign=None, xyz_ws=None):
     B, N = x.shape[0], x.shape[2]
     M = B * N
     k = net.k
@@ -512,15 +521,28 @@ def _lpdnet_features_eval_body(net, x, mfea, use_side, assign=None):
     else:
         xyz = x.view(M, 3)
         p = xyz
+    # the static graph feeds the cloud-resident K-agg alone on the panel route: the search writes the packed uint16 lists itself
+    # (ops.knn_pm16) and the int32 lists only for the DEBUG_AUX hooks
+    xyz16 = PANEL_LAYOUT and N % 128 == 0 and _resident_shape(k, N, M, act) and ops.knn_pm16_fused(3, N, k)
+
+    def xyz_graph():
+        # xyz_ws: the sort at the head of the forward left this search's operands and tile statistics in its workspace
+        if xyz16:
+            return ops.knn_pm16(None if xyz_ws is not None else xyz.reshape(M, 3), B, N, k, want_idx=_TLS.DEBUG_AUX is not None, ws=xyz_ws)
+        return (ops.knn_prepared(xyz_ws, B, N, k, C=3) if xyz_ws is not None else _knn_rows(xyz, B, N, 3, k)), None
+
     side_job = None
     if use_side:
         # The static graph in Cartesian space depends on the input alone: its kNN (wave-slot-bound, two waves per SIMD) runs
         # on a second HIP stream next to the per-point layers and the feature-space kNN and is joined in front of the SN1 K-agg.
         main, side = torch.cuda.current_stream(), _side_stream(x.device)
         _join(side, main)
+        if xyz_ws is not None:
+            xyz_ws.record_stream(side)
         with torch.cuda.stream(side):
-            idx_x = _knn_rows(xyz, B, N, 3, k)
-            i16_x = ops.pack_idx16(idx_x)
+            idx_x, i16_x = xyz_graph()
+            if i16_x is None:
+                i16_x = ops.pack_idx16(idx_x)
         side_job = (side, idx_x, i16_x)
     knn_ws = None
     if FUSED_FRONT and not (mfea or net.t3d or net.tfea) and N % 128 == 0 and k <= 64:
@@ -606,11 +628,13 @@ def _lpdnet_features_eval_body(net, x, mfea, use_side, assign=None):
             side, idx_x, i16_x = side_job
             main = torch.cuda.current_stream()
             _join(main, side)
-            idx_x.record_stream(main)
+            if idx_x is not None:
+                idx_x.record_stream(main)
             i16_x.record_stream(main)
         else:
-            idx_x = _knn_rows(xyz, B, N, 3, k)      # static graph in Cartesian space (raw xyz even when t3d, :226,255)
-            i16_x = pack(idx_x)
+            idx_x, i16_x = xyz_graph()              # static graph in Cartesian space (raw xyz even when t3d, :226,255)
+            if i16_x is None:
+                i16_x = pack(idx_x)
         kagg_p(pq3[:, 0:32], pq3[:, 32:64], i16_x, N, scale=s3, shift=b3, act=act, slope=slope, out=x3v)
         if _TLS.DEBUG_AUX is not None:
             _TLS.DEBUG_AUX.update(F0=f, idx_feat=idx_f, idx_xyz=idx_x, cat=ops.split_to_rows(cat) if split else ops.panels_to_rows(cat))
@@ -637,7 +661,7 @@ def _lpdnet_features_eval_body(net, x, mfea, use_side, assign=None):
         _join(torch.cuda.current_stream(), side)
         idx_x.record_stream(torch.cuda.current_stream())
     else:
-        idx_x = _knn_rows(x.view(B * N, 3), B, N, 3, k)
+        idx_x = xyz_graph()[0]
     pq = ops.linear(cat[:, 128:256], split_edge_weight(net.convSN1, "cat_nc"))          # [M,512]
     kagg(pq[:, :256], pq[:, 256:], idx_x, N, scale=s3, shift=b3, act=act, slope=slope, out=cat[:, 256:512])
     if _TLS.DEBUG_AUX is not None:
@@ -654,7 +678,7 @@ def _aligned_input(xyz_t, p_all, mfea):
 def lpdnet_origin_features_eval(net, x, reorder=True):
     """util/lpdnet_model.py:68-114 (LPDNetOrign.forward), eval mode."""
     mfea = getattr(net, "use_mFea", False)
-    x = _check_input(x, 8) if mfea else reorder_points(_check_input(x), reorder)
+    x, xyz_ws = (_check_input(x, 8), None) if mfea else reorder_points_knn(_check_input(x), reorder, net.k)
     B, N = x.shape[0], x.shape[2]
     M = B * N
     k = net.k
@@ -682,7 +706,7 @@ def lpdnet_origin_features_eval(net, x, reorder=True):
     s1, b1 = bn_affine(net.convDG1[1])
     s2, b2 = bn_affine(net.convDG2[1])
     g = ops.edge_mlp(pq[:, :64], pq[:, 64:], idx_f, N, s1, b1, _w2d(net.convDG2[0]), s2, b2, act=act, slope=slope)
-    idx_x = _knn_rows(x.view(B * N, 3), B, N, 3, k)
+    idx_x = ops.knn_prepared(xyz_ws, B, N, k, C=3) if xyz_ws is not None else _knn_rows(x.view(B * N, 3), B, N, 3, k)
     pn = ops.linear(g, split_edge_weight(net.convSN1, "nbr"))                           # [M,64] neighbours only
     s1, b1 = bn_affine(net.convSN1[1])
     s2, b2 = bn_affine(net.convSN2[1])

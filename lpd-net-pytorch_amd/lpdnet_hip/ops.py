@@ -206,13 +206,13 @@ def lpdnet_front(xyz, W1, s1, b1, W2, s2, b2, B, N, k, act=ACT_NONE, slope=0.01)
 KNN_PM_PREPARED = 256
 
 
-def knn_prepared(ws, B, N, k, impl=None):
-    """kNN graph from the operands lpdnet_front left in ws (64 channels)."""
+def knn_prepared(ws, B, N, k, impl=None, C=64):
+    """kNN graph from the operands lpdnet_front (64 channels) or morton_sort_knn (C=3) left in ws."""
     if impl is None:
         impl = KNN_IMPL
     idx = torch.empty((B, N, k), dtype=torch.int32, device=ws.device)
     lib = _lib.load()
-    _call(f"knn[C=64,k={k}]", lib.lpd_knn_pm, None, 64, B, 64, N, k, _ptr(idx), _ptr(ws), impl | KNN_PM_PREPARED, _stream())
+    _call(f"knn[C={C},k={k}]", lib.lpd_knn_pm, None, C, B, C, N, k, _ptr(idx), _ptr(ws), impl | KNN_PM_PREPARED, _stream())
     return idx
 
 
@@ -232,7 +232,38 @@ def knn_pm(x_pm, B, N, k, impl=None):
     return idx
 
 
-# Dense products run as split-bf16 ("bf16x3": three bf16 MFMA products per term, fp32 accumulate; ~2e-6 on the
+def knn_pm16_fused(C, N, k, impl=None):
+    """does the search on these sizes write the packed uint16 lists from its own final merge (then the int32 lists are optional)?"""
+    return bool(k == 20 and N % 32 == 0 and _lib.load().lpd_knn_pm16_fused(C, N, k, KNN_IMPL if impl is None else impl))
+
+
+def knn_pm16(x_pm, B, N, k, want_idx=True, impl=None, ws=None, C=3):
+    """knn_pm whose lists also leave as pack_idx16's blocked uint16 copy (k = 20, N % 32 == 0): -> (idx or None, idx16).  Where
+    knn_pm16_fused says so the search writes the blocks itself and want_idx=False drops the int32 lists; elsewhere both come back
+    (the search, then the pack_idx16 launch).  x_pm None: the operands of C channels are in ws already (morton_sort_knn, lpdnet_front)."""
+    if impl is None:
+        impl = KNN_IMPL
+    if x_pm is None:
+        if ws is None:
+            raise ValueError("knn_pm16: prepared operands need their workspace")
+        ld, M, dev = C, B * N, ws.device
+        impl |= KNN_PM_PREPARED
+    else:
+        ld = _rows(x_pm, "x_pm")
+        M, C = x_pm.shape
+        dev = x_pm.device
+        ws = torch.empty((knn_workspace_floats(B, C, N),), dtype=torch.float32, device=dev)
+    if M != B * N or k != 20 or N % 32:
+        raise ValueError("knn_pm16: rows != B*N, k != 20 or N % 32 != 0")
+    lib = _lib.load()
+    want_idx = bool(want_idx) or not lib.lpd_knn_pm16_fused(C, N, k, impl)
+    idx = torch.empty((B, N, k), dtype=torch.int32, device=dev) if want_idx else None
+    idx16 = torch.empty((M, k), dtype=torch.int16, device=dev)
+    _call(f"knn[C={C},k={k}]", lib.lpd_knn_pm16, _ptr(x_pm), ld, B, C, N, k, _ptr(idx), _ptr(idx16), _ptr(ws), impl, _stream())
+    return idx, idx16
+
+
+# Dense products run as split-bf16 ("bf16x3":three bf16 MFMA products per term, fp32 accumulate; ~2e-6 on the
 # descriptors, csrc/lpd_gemm.hip) unless the call asks for exact fp32 (layers whose output feeds the kNN) or this switch
 # is off (LPD_GEMM_FP32=1: every product on the f32-input MFMA, bit-for-bit the round-1 numerics).
 GEMM_BF16X3 = __import__("os").environ.get("LPD_GEMM_FP32", "0") != "1"
@@ -1073,6 +1104,27 @@ def morton_sort(x, want_perm=False):
     _call("morton_sort", lib.lpd_morton_sort, _ptr(x3), _ptr(out), _ptr(perm), B, N, _stream())
     out = out.view(shape)
     return (out, perm) if want_perm else out
+
+
+def morton_sort_knn_applies(N, k):
+    """does the sort also prepare the xyz search's workspace on these sizes (N % 32 == 0, 64 <= N <= 16384, best-first search)?"""
+    return bool(_lib.load().lpd_morton_sort_knn_applies(int(N), int(k)))
+
+
+def morton_sort_knn(x, k, want_perm=False):
+    """morton_sort that also leaves the xyz search's operands and tile statistics of the sorted clouds in a kNN workspace
+    (lpd_morton_sort_knn): -> (sorted x, ws[, perm]); pass ws to knn_prepared(ws, B, N, k, C=3) or knn_pm16(None, ..., ws=ws)."""
+    _req(x, "x")
+    shape = x.shape
+    x3 = x.reshape(-1, shape[-2], 3).contiguous()
+    B, N = x3.shape[0], x3.shape[1]
+    out = torch.empty_like(x3)
+    perm = torch.empty((B, N), dtype=torch.int32, device=x.device) if want_perm else None
+    ws = torch.empty((knn_workspace_floats(B, 3, N, k),), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    _call("morton_sort", lib.lpd_morton_sort_knn, _ptr(x3), _ptr(out), _ptr(perm), B, N, k, _ptr(ws), _stream())
+    out = out.view(shape)
+    return (out, ws, perm) if want_perm else (out, ws)
 
 
 def local_features(xyz_rows, idx, B, N, *, candidates=None, columns=range(10), copy_xyz=False, want_k=False, out=None):
