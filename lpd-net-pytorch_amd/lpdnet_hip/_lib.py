@@ -1,4 +1,7 @@
-"""ctypes binding of liblpd_hip.so (C-ABI declared in include/lpd_hip.h).
+"""ctypes binding of liblpd_hip.so.  include/lpd_hip.h is the only description of the C-ABI: the argument and return types of
+every entry point (SIGNATURES, _RESTYPES) and the integer constants it defines (DEFINES) are read from its text once, when this
+module is imported.  A prototype outside the header's closed grammar raises instead of being guessed; tests/test_abi.py holds the
+result to what a C++ compiler reads in the same header.
 
 torch is imported first on purpose: liblpd_hip.so needs libamdhip64.so.7, and the dynamic loader
 then reuses the HIP runtime torch already loaded (same SONAME), so device pointers and stream
@@ -9,177 +12,78 @@ non-CUDA tensors.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must precede CDLL, see above)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LPD_HIP_LIB") or os.path.join(_HERE, "liblpd_hip.so")   # override: kernel-variant builds (tools/)
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "lpd_hip.h")      # = _build.PUBLIC_HEADER
 
 _c_int = ctypes.c_int
 _c_ll = ctypes.c_longlong
 _c_f = ctypes.c_float
 _c_p = ctypes.c_void_p
 
-# name -> argtypes (restype is int unless listed in _RESTYPES)
-SIGNATURES = {
-    "lpd_version": [],
-    "lpd_last_error": [],
-    "lpd_stat_ws_bytes": [],
-    "lpd_knn": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_int, _c_p],
-    "lpd_gemm": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                 _c_ll, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-"lpd_gemm_bf16x3": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                 _c_ll, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_bf16x1": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                 _c_ll, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_prep_b_bytes": [_c_int, _c_int],
-    "lpd_gemm_prep_b": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p],
-    "lpd_gemm_prep_b_batch": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_p, _c_p],
-    "lpd_gemm_x3t_applies": [_c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int],
-    "lpd_gemm_x3t_rows_applies": [_c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll],
-    "lpd_gemm_x3t_rows": [_c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int, _c_ll, _c_ll, _c_ll,
-                          _c_p],
-    "lpd_gemm_x3t": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_f, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_x3w": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int,
-                     _c_ll, _c_ll, _c_int, _c_int, _c_int, _c_p],
-    "lpd_gemm_p8_applies": [_c_int, _c_int, _c_int, _c_int],
-    "lpd_gemm_p8": [_c_p, _c_p, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p,
-                    _c_int, _c_f, _c_int, _c_p],
-    "lpd_gemm_p8_fused": [_c_p, _c_p, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p,
-                          _c_int, _c_f, _c_p, _c_p, _c_ll, _c_p],
-    "lpd_softmax_affine_parts": [_c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p],
-    "lpd_split_panels": [_c_p, _c_ll, _c_int, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_p],
-    "lpd_gemm_x3w_batched": [_c_p, _c_int, _c_int, _c_p, _c_ll, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_int, _c_f, _c_int, _c_p],
-    "lpd_gemm_x3w_bf16a": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p],
-    "lpd_gemm_x3w_act": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_f, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_gemm_x3w_stats": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p],
-    "lpd_retrieval_topk": [_c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_recall_pairs": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p,
-                         _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_f64_to_f32": [_c_p, _c_p, _c_ll, _c_p],
-    "lpd_best_pos_bwd": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p],
-    "lpd_hard_negatives": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p],
-    "lpd_knn_pm_layout": [_c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_lpdnet_front": [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p],
-    "lpd_knn_pm": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_int, _c_p],
-    "lpd_knn_pm16_fused": [_c_int, _c_int, _c_int, _c_int],
-    "lpd_idx16_offset": [_c_ll, _c_int],
-    "lpd_knn_pm16": [_c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_p],
-    "lpd_knn_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
-    "lpd_edge_gather_max": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
-                            _c_int, _c_int, _c_f, _c_p],
-    "lpd_edge_gather_max16": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
-                              _c_int, _c_int, _c_f, _c_ll, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_edge_gather_max16s": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_ll, _c_p, _c_p, _c_int, _c_int, _c_int,
-                               _c_int, _c_int, _c_f, _c_ll, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_edge_mlp_x1_bf16x3s": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_int,
-                                _c_f, _c_ll, _c_int, _c_p],
-    "lpd_edge_mlp_bf16x3s": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int,
-                             _c_int, _c_int, _c_int, _c_int, _c_f, _c_ll, _c_int, _c_p],
-    "lpd_gemm_x3ts": [_c_p, _c_ll, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_f, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_pack_idx16": [_c_p, _c_p, ctypes.c_longlong, _c_int, _c_p],
-    "lpd_pack_idx16w": [_c_p, _c_p, ctypes.c_longlong, _c_int, _c_int, _c_p],
-    "lpd_edge_gather_maxw": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int,
-                             _c_int, _c_int, _c_f, _c_ll, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_edge_mlp": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
-                     _c_int, _c_int, _c_int, _c_int, _c_f, _c_ll, _c_int, _c_p],
-    "lpd_edge_mlp_bf16x3": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
-                     _c_int, _c_int, _c_int, _c_int, _c_f, _c_ll, _c_int, _c_p],
-    "lpd_linear_smallk": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_ll, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int,
-                          _c_p, _c_p, _c_p, _c_int, _c_f, _c_p],
-    "lpd_transpose": [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_p],
-    "lpd_softmax_affine": [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_p, _c_p],
-    "lpd_vlad_finalize": [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p],
-    "lpd_colmax": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_mul": [_c_p, _c_p, _c_p, _c_ll, _c_p],
-    "lpd_gating": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_morton_sort": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_p],
-    "lpd_morton_sort_knn_applies": [_c_int, _c_int],
-    "lpd_morton_sort_knn": [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p],
-    "lpd_local_features": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int, ctypes.c_uint, _c_int, _c_p, _c_int, _c_p, _c_p],
-    "lpd_make_submaps": [_c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_sample_items": [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_int, ctypes.c_ulonglong, _c_p, _c_p,
-                         _c_p],
-    "lpd_gather_tuples": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_f, _c_f, ctypes.c_ulonglong, _c_p, _c_p],
-    "lpd_radius_count": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p],
-    "lpd_radius_fill": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_int, ctypes.c_double, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p],
-    "lpd_road_planes_workspace_bytes": [_c_int, _c_int],
-    "lpd_road_planes": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_clean_count": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_clean_fill": [_c_p, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_colstats": [_c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_bn_finalize": [_c_p, _c_p, ctypes.c_double, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_affine_act": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p],
-    "lpd_affine_act2": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p],
-    "lpd_bn_act_bwd": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int,
-                       _c_p, _c_p, _c_p, _c_p],
-    "lpd_bn_act_bwd_bf16": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int,
-                       _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_build": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_group_max": [_c_p, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p, _c_ll, _c_p, _c_ll, _c_int, _c_p],
-    "lpd_group_max_sel": [_c_p, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_edge_bn_bwd_sel": [_c_p, _c_ll, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_int, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f,
-                            _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_bn_bwd_bf16_sel": [_c_p, _c_ll, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_int, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f,
-                                 _c_p, _c_p, _c_p, _c_p],
-    "lpd_group_max_bwd": [_c_p, _c_ll, _c_p, _c_int, _c_p, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_edge_bn_bwd": [_c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int,
-                        _c_f, _c_f, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_mlp_train_bwd": [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_p, _c_p,
-                               _c_p, _c_p, _c_int, _c_int, _c_int, _c_f, _c_f, _c_p, _c_p, _c_p],
-    "lpd_edge_dense_bwd_apply": [_c_p, _c_int, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_int,
-                                 _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_mlp_train": [_c_p, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p, _c_int, _c_p, _c_p, _c_p,
-                           _c_int, _c_int, _c_int, _c_int, _c_f, _c_p, _c_p],
-    "lpd_group_sum": [_c_p, _c_int, _c_p, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_scatter_add_rows": [_c_p, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_int, _c_int, _c_p],
-    "lpd_graph_transpose": [_c_p, _c_ll, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_gather_sum_rows": [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_dw_smallk": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_int, _c_p, _c_p],
-    "lpd_colmax_arg": [_c_p, _c_ll, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_colmax_bwd": [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p],
-    "lpd_cloud_outer": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_softmax_bwd": [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_vlad_finalize_bwd": [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p],
-    "lpd_edge_split_fwd": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_split_bwd": [_c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_ll,
-                           _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_split_fwd16_applies": [_c_int, _c_int, _c_int],
-    "lpd_edge_split_fwd16": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_build_bf16": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_act_max": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_int, _c_p],
-    "lpd_edge_act_max_bf16": [_c_p, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_int, _c_p],
-    "lpd_group_sel_stats_bf16": [_c_p, _c_int, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_bn_bwd_bf16": [_c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int,
-                             _c_f, _c_f, _c_p, _c_p, _c_p, _c_p],
-    "lpd_bn_sel_bwd_reduce": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_dw_sel_bf16": [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_gemm_bf16s_bnbwd": [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_bn_sel_bwd_reduce_f32": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_edge_dw_sel_f32": [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_gemm_f32s_bnbwd": [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-    "lpd_gather_sum_rows_bf16": [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_bf16s": [_c_p, _c_p, _c_int, _c_int, _c_p, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_tn_bf16_ws_floats": [_c_ll, _c_int, _c_int],
-    "lpd_edge_dw_sel_bf16_ws_bytes": [_c_ll],
-    "lpd_gemm_tn_bf16": [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p],
-    "lpd_gemm_tn_ws_floats": [_c_ll, _c_int, _c_int, _c_int],
-    "lpd_gemm_tn": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p],
-    "lpd_gemm_tn_act": [_c_p, _c_ll, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_ll, _c_ll, _c_int, _c_p, _c_p, _c_int, _c_f, _c_p],
-    "lpd_gemm_tn_act_ws_floats": [_c_ll, _c_int, _c_int, _c_int, _c_int],
-    "lpd_metric_loss": [_c_p, _c_ll, _c_p, _c_ll, _c_ll, _c_p, _c_ll, _c_ll, _c_p, _c_ll, _c_int, _c_int, _c_int,
-                        _c_int, _c_f, _c_f, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p],
-}
-_RESTYPES = {"lpd_last_error": ctypes.c_char_p, "lpd_stat_ws_bytes": ctypes.c_longlong, "lpd_knn_workspace_floats": ctypes.c_longlong, "lpd_idx16_offset": ctypes.c_longlong,
-             "lpd_gemm_prep_b_bytes": ctypes.c_longlong, "lpd_gemm_tn_bf16_ws_floats": ctypes.c_longlong, "lpd_gemm_tn_ws_floats": ctypes.c_longlong,
-             "lpd_gemm_tn_act_ws_floats": ctypes.c_longlong,
-             "lpd_edge_dw_sel_bf16_ws_bytes": ctypes.c_longlong, "lpd_road_planes_workspace_bytes": ctypes.c_longlong}
-
-_lib = None
+# the header's whole type vocabulary; every parameter whose type contains `*` is a c_void_p
+_SCALARS = {"int": _c_int, "int32_t": _c_int, "long long": _c_ll, "int64_t": _c_ll,
+            "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "uint32_t": ctypes.c_uint,
+            "unsigned long long": ctypes.c_ulonglong, "uint64_t": ctypes.c_ulonglong, "float": _c_f, "double": ctypes.c_double}
+_RETURNS = {"int": _c_int, "long long": _c_ll, "const char*": ctypes.c_char_p}
+_TYPE_WORDS = {w for t in _SCALARS for w in t.split()} | {"long", "short", "char", "signed", "void"}      # never a parameter's name
 
 
 class LpdHipError(RuntimeError):
     pass
+
+
+def _param_type(param):
+    if "*" in param:
+        return _c_p
+    words = [w for w in param.split() if w != "const"]
+    for n in (3, 2, 1):      # the longest type first; what is left is at most the parameter's name
+        ctype, name = _SCALARS.get(" ".join(words[:n])), words[n:]
+        if ctype and (not name or (len(name) == 1 and name[0].isidentifier() and name[0] not in _TYPE_WORDS)):
+            return ctype
+    return None
+
+
+def parse_header(text):
+    """(SIGNATURES, _RESTYPES, DEFINES) of a header's text: name -> argtypes of every prototype `ret lpd_name(params);`, the returns
+    that are not int, and every `#define LPD_NAME <integer literal>`."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)      # the comments hold call-like text
+    defines = {m[1]: int("".join(m[2].split()), 0) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(LPD_\w+)[ \t]+\(?[ \t]*(-?[ \t]*(?:0[xX][0-9a-fA-F]+|[1-9][0-9]*|0))[ \t]*\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    signatures, restypes = {}, {}
+    for m in re.finditer(r"([^;{}]*?)\b(lpd_\w+)\s*\(([^;{}]*)\)\s*;", text):      # everything since the last statement is the return type
+        ret, name, params = re.sub(r"\s*\*\s*", "*", " ".join(m[1].split())), m[2], m[3]
+        if name in signatures:
+            raise LpdHipError(f"lpd_hip.h declares {name} twice")
+        if ret not in _RETURNS:
+            raise LpdHipError(f"lpd_hip.h: {name}: no ctypes type for the return type {ret!r}")
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        argtypes = [None if "(" in p or ")" in p or "[" in p else _param_type(p) for p in params]
+        if None in argtypes:
+            raise LpdHipError(f"lpd_hip.h: {name}: no ctypes type for the parameter {params[argtypes.index(None)]!r}")
+        signatures[name] = argtypes
+        if _RETURNS[ret] is not _c_int:
+            restypes[name] = _RETURNS[ret]
+    return signatures, restypes, defines
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as fh:
+            return parse_header(fh.read())
+    except OSError as e:
+        raise LpdHipError(f"{HEADER_PATH}: the public header is not readable ({e}); the binding is derived from it") from None
+
+
+# name -> argtypes (restype is int unless listed in _RESTYPES); LPD_* name -> value
+SIGNATURES, _RESTYPES, DEFINES = _read_header()
+
+_lib = None
 
 
 def load():

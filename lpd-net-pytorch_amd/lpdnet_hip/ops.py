@@ -9,7 +9,7 @@ import torch
 
 from . import _debug, _lib
 
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = (_lib.DEFINES["LPD_ACT_" + n] for n in ("NONE", "RELU", "LEAKY", "SIGMOID"))
 
 class _PerThread(__import__("threading").local):
     """Measurement hooks, per host thread (a profile opened by one thread must not collect another thread's launches); read and
@@ -203,7 +203,7 @@ def lpdnet_front(xyz, W1, s1, b1, W2, s2, b2, B, N, k, act=ACT_NONE, slope=0.01)
     return f0, ws
 
 
-KNN_PM_PREPARED = 256
+KNN_PM_PREPARED = _lib.DEFINES["LPD_KNN_PM_PREPARED"]
 
 
 def knn_prepared(ws, B, N, k, impl=None, C=64):
@@ -1363,7 +1363,8 @@ def radius_lists(qpos, dpos, radius, seg_off=None, skip_seg=None, self_item=None
     return off, idx, counts
 
 
-CLEAN_MAX_H, CLEAN_MAX_RANGE, CLEAN_CHUNK = 1024, 512.0, 1024      # csrc/lpd_clean_math.h
+CLEAN_MAX_H, CLEAN_MAX_RANGE = 1024, 512.0      # csrc/lpd_clean_math.h
+CLEAN_CHUNK = _lib.DEFINES["LPD_CLEAN_CHUNK"]
 
 
 class CleanParams(ctypes.Structure):
