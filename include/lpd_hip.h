@@ -605,6 +605,48 @@ int lpd_clean_fill(const float* points, int ld, int rows, const int32_t* offsets
                    const float* plane, const int32_t* info, const int32_t* block_off, float* out, int32_t* out_offsets,
                    unsigned char* mask, void* stream);
 
+/*
+ * Submaps from a drive (csrc/lpd_drive.hip; arithmetic in csrc/lpd_drive_math.h): posed scans cut by distance travelled into windows,
+ * each window brought into one frame.  The reference's .bin submaps and its pointcloud_locations_20m_10overlap.csv (20 m windows every
+ * 10 m for training, every 20 m for testing) come from an offline step that is not part of it; this comment is the specification, and
+ * lpd_drive_math.h settles every detail it leaves open.  The step in front of lpd_clean_* and lpd_make_submaps; no read-back.
+ *   points   [rows][ld] fp32, ld >= 3, three coordinates used, each scan in its own sensor frame
+ *   offsets  DEVICE int32 [S+1]: scan i is rows offsets[i] .. offsets[i+1]-1 (a scan may have no rows)
+ *   poses    [S][12] float64 on the device: the top three rows of the homogeneous sensor-to-world matrix, row-major (R | t) -- a line of
+ *            a KITTI poses.txt.  Float64 is part of the definition: at a UTM northing of 5.7e6 an fp32 ulp is 0.5 m.
+ * Float64 and fp32 alike: every operation rounded once, nothing contracted; every dot product is ((a0*b0) + (a1*b1)) + (a2*b2).
+ *  1 Steps.    dl_0 = 0;  d = t_i - t_{i-1},  dl_i = sqrt(((dx*dx) + (dy*dy)) + (dz*dz)) in float64 with the correctly rounded square
+ *              root;  q_i = (int64) rint(dl_i * 65536.0) clamped to [0, 2^36];  a dl_i that is not finite gives q_i = 0.  Distances are
+ *              integers in units of 2^-16 m from here on: their sums are exact in any order.
+ *  2 Distance. D_i = q_0 + ... + q_i (the caller's: torch.cumsum on int64 in lpdnet_hip/ops.py).
+ *  3 Windows.  L = rint(length * 65536), T = rint(stride * 65536) (the caller's, 1 <= L, T <= 2^40).  lower_bound(D, v) = the first i
+ *              with D_i >= v, S when there is none.  Window w is the scans first_w = lower_bound(D, w*T) .. end_w - 1 with
+ *              end_w = lower_bound(D, w*T + L): a scan with D_i == w*T + L belongs to the next range.  Its reference scan is
+ *              ref_w = min(lower_bound(D, w*T + L/2), end_w - 1), L/2 the integer quotient.  first_w == end_w is an EMPTY window (a
+ *              single step longer than L): ref = -1, no rows, position 0.  The windows of the drive are the w with w*T + L <= D_{S-1};
+ *              a window behind them is written as (S, S, -1, 0), empty.  A scan lies in at most ceil(L / T) windows.
+ *  4 Plan.     plan [W][4] int32 = (first, end, ref, rows), rows = offsets[end] - offsets[first]: a window's rows are ONE contiguous
+ *              range of the input rows.  position [W][3] float64 = t_ref, bit-copies.  The output offsets are the exclusive scan of
+ *              `rows` (the caller's torch.cumsum again).
+ *  5 Relative pose of scan i in window w, float64:  frame = 1 (the reference scan's own frame)  M = R_ref^T R_i,
+ *              u = R_ref^T (t_i - t_ref);  frame = 0 (world axes moved to the reference scan's position)  M = R_i, u = t_i - t_ref.
+ *              The difference is taken first (three subtractions); the twelve numbers are rounded to fp32 once.
+ *  6 Rows.     out_c = (((M_c0*x) + (M_c1*y)) + (M_c2*z)) + u_c in fp32.  A NaN or inf coordinate passes through as the arithmetic
+ *              gives it (the cleaning behind drops it); the scan of a row is the last i with offsets[i] <= row.
+ * lpd_drive_steps writes q [S] int64.  lpd_drive_plan writes plan and position for the windows w0 .. w0+W-1 (a long drive is planned in
+ * batches; w0 >= 0, w0 + W <= 2^22).  lpd_drive_rows writes out [out_off[W]][3]: the rows of window 0 of the call at out_off[0], ...;
+ * out_off DEVICE int32 [W+1]; max_len (1 .. 2^20) is the caller's bound on the longest window and sizes the grid.  A window is NOT
+ * WRITTEN when its rows exceed max_len, when its plan line is not one (not 0 <= first <= ref < end <= S, rows != offsets[end] -
+ * offsets[first], input rows outside [0, rows)) or when out_off[w+1] - out_off[w] != rows or out_off[w] < 0.  Nothing outside [0, S) of
+ * the poses, [0, S] of the offsets and [0, rows) of the points is ever read, whatever the tables hold; no row is used as an address.
+ * No atomics: the same bits in every launch.  Limits: 1 <= S <= 2^22, 1 <= W <= 65535 per call, fewer than 2^31 output rows.
+ */
+int lpd_drive_steps(const double* poses, int S, long long* q, void* stream);
+int lpd_drive_plan(const long long* D, int S, const int32_t* offsets, const double* poses, long long L, long long T, long long w0, int W,
+                   int32_t* plan, double* position, void* stream);
+int lpd_drive_rows(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, const int32_t* plan, int W,
+                   const int32_t* out_off, int frame, int max_len, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -11,6 +11,7 @@ host, and the host does no per-element work.
                                  the same for RAW scans of any length (no counterpart in the reference): rows of float64 xyz or
                                  KITTI-style float32 x 4, made into submaps on the device (submap.make_submaps)
   evaluate_model_from_sets       evaluate.evaluate_model on the reference's pickled DATABASE_SETS / QUERY_SETS
+  load_poses                     a KITTI-style poses file (twelve numbers per line) -> [S, 12] float64, for lpdnet_hip.drive
 """
 import os
 
@@ -115,6 +116,29 @@ def load_scan_file(filename, dataset_folder="", dtype=np.float64, columns=3):
     if columns < 3 or pc.shape[0] == 0 or pc.shape[0] % columns:
         return np.array([])
     return np.reshape(pc, (pc.shape[0] // columns, columns))
+
+
+def load_poses(path, dataset_folder=""):
+    """A KITTI-style poses file -- one scan per line, twelve numbers: the top three rows of the sensor-to-world matrix, row-major --
+    -> [S, 12] float64, what drive.plan_windows / accumulate / submaps_from_drive take.  Blank lines and lines that start with `#` are
+    skipped; any other line that does not hold twelve numbers raises ValueError with its line number."""
+    rows = []
+    with open(os.path.join(dataset_folder, path)) as fh:
+        for no, line in enumerate(fh, 1):
+            text = line.strip()
+            if not text or text.startswith("#"):
+                continue
+            fields = text.replace(",", " ").split()
+            try:
+                vals = [float(f) for f in fields]
+            except ValueError:
+                raise ValueError(f"{path}:{no}: not a number in {text[:60]!r}") from None
+            if len(vals) != 12:
+                raise ValueError(f"{path}:{no}: {len(vals)} numbers, a pose line holds 12")
+            rows.append(vals)
+    if not rows:
+        raise ValueError(f"{path}: no poses")
+    return np.asarray(rows, dtype=np.float64)
 
 
 class ScanStream:

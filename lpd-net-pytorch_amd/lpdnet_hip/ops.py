@@ -1437,6 +1437,107 @@ def clean_scans(points, offsets, B, max_len, params, plane=None, info=None, want
     return out, out_offsets, mask
 
 
+DRIVE_MAX_SCANS, DRIVE_MAX_WINDOWS, DRIVE_MAX_WINDOW_NO, DRIVE_MAX_UNITS = 1 << 22, 65535, 1 << 22, 1 << 40      # csrc/lpd_drive_math.h
+DRIVE_UNITS_PER_METRE = 65536
+
+
+def drive_units(metres, what):
+    """A length in metres -> the integer number of 2^-16 m units the windows are cut in (rint, half to even; 1 .. 2^40)"""
+    metres = float(metres)
+    if not (metres > 0.0 and metres < float("inf")):
+        raise ValueError(f"{what}={metres} (finite, > 0)")
+    units = int(round(metres * DRIVE_UNITS_PER_METRE))      # Python's round is half to even, the product is exact (a power of two)
+    if not 1 <= units <= DRIVE_MAX_UNITS:
+        raise ValueError(f"{what}={metres} m is {units} units of 2^-16 m; 1 .. 2^40")
+    return units
+
+
+def _drive_poses(what, poses):
+    _req(poses, "poses", torch.float64)
+    if poses is None:
+        raise TypeError(f"{what}: poses is a tensor")
+    if poses.dim() != 2 or poses.shape[1] != 12 or not 1 <= poses.shape[0] <= DRIVE_MAX_SCANS:
+        raise ValueError(f"{what}: poses must be [S, 12] with 1 <= S <= 2^22, got {tuple(poses.shape)}")
+    return poses.contiguous(), poses.shape[0]
+
+
+def drive_distance(poses):
+    """The distance travelled up to every scan in units of 2^-16 m (lpd_drive_steps, then a torch.cumsum on int64; definition in
+    include/lpd_hip.h): poses [S, 12] float64 on the device -> (q [S] int64, D [S] int64).  Nothing is read back."""
+    poses, S = _drive_poses("drive_distance", poses)
+    q = torch.empty((S,), dtype=torch.int64, device=poses.device)
+    _call("drive_steps", _lib.load().lpd_drive_steps, _ptr(poses), S, _ptr(q), _stream())
+    return q, torch.cumsum(q, 0)
+
+
+def _drive_offsets(what, offsets, S):
+    _req(offsets, "offsets", torch.int32)
+    if offsets is None or offsets.dim() != 1 or offsets.numel() != S + 1:
+        raise ValueError(f"{what}: offsets must hold S+1 = {S + 1} entries, got {None if offsets is None else tuple(offsets.shape)}")
+    return offsets.contiguous()
+
+
+def drive_plan(D, offsets, poses, L, T, w0, W):
+    """The windows w0 .. w0+W-1 of a drive (lpd_drive_plan): D [S] int64 from drive_distance, offsets [S+1] int32 on the device, L / T
+    the window's length and stride in units (drive_units) -> (plan [W, 4] int32 = (first, end, ref, rows), position [W, 3] float64).
+    1 <= W <= 65535 per call; a window behind the drive's last one comes out empty.  Nothing is read back."""
+    poses, S = _drive_poses("drive_plan", poses)
+    _req(D, "D", torch.int64)
+    if D is None or tuple(D.shape) != (S,):
+        raise ValueError(f"drive_plan: D must be [S] = ({S},), got {None if D is None else tuple(D.shape)}")
+    offsets = _drive_offsets("drive_plan", offsets, S)
+    L, T, w0, W = int(L), int(T), int(w0), int(W)
+    if not (1 <= L <= DRIVE_MAX_UNITS and 1 <= T <= DRIVE_MAX_UNITS):
+        raise ValueError(f"drive_plan: L={L} T={T} outside 1 .. 2^40")
+    if not 1 <= W <= DRIVE_MAX_WINDOWS or w0 < 0 or w0 + W > DRIVE_MAX_WINDOW_NO:
+        raise ValueError(f"drive_plan: windows {w0} .. {w0 + W} (1 <= W <= {DRIVE_MAX_WINDOWS} per call, at most 2^22 in all)")
+    plan = torch.empty((W, 4), dtype=torch.int32, device=poses.device)
+    position = torch.empty((W, 3), dtype=torch.float64, device=poses.device)
+    _call("drive_plan", _lib.load().lpd_drive_plan, _ptr(D.contiguous()), S, _ptr(offsets), _ptr(poses), L, T, w0, W, _ptr(plan), _ptr(position),
+          _stream())
+    return plan, position
+
+
+def drive_rows(points, offsets, poses, plan, out_off, max_len, out_rows, frame=1, out=None):
+    """The rows of W windows in their reference scans' frames (lpd_drive_rows): points [rows, >=3] fp32 with contiguous rows, offsets
+    [S+1] int32, poses [S, 12] float64, plan [W, 4] int32 and out_off [W+1] int32 (the exclusive scan of plan[:, 3]) on the device;
+    max_len = the host-known longest window (it sizes the grid; a longer window is not written); out_rows = the host-known
+    out_off[W].  frame 1: the reference scan's own frame, 0: world axes at its position.  -> out [out_rows, 3] fp32.  Nothing is read
+    back."""
+    _req(points, "points")
+    _req(plan, "plan", torch.int32)
+    _req(out_off, "out_off", torch.int32)
+    poses, S = _drive_poses("drive_rows", poses)
+    if points is None or plan is None or out_off is None:
+        raise TypeError("drive_rows: points, plan and out_off are tensors")
+    ld = _rows(points, "points")
+    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
+        raise ValueError(f"drive_rows: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    offsets = _drive_offsets("drive_rows", offsets, S)
+    if plan.dim() != 2 or plan.shape[1] != 4 or not 1 <= plan.shape[0] <= DRIVE_MAX_WINDOWS:
+        raise ValueError(f"drive_rows: plan must be [W, 4] with 1 <= W <= {DRIVE_MAX_WINDOWS}, got {tuple(plan.shape)}")
+    W = plan.shape[0]
+    if tuple(out_off.shape) != (W + 1,):
+        raise ValueError(f"drive_rows: out_off must be [W+1] = ({W + 1},), got {tuple(out_off.shape)}")
+    if frame not in (0, 1):
+        raise ValueError(f"drive_rows: frame={frame!r} (0 or 1)")
+    max_len, out_rows = int(max_len), int(out_rows)
+    if not 1 <= max_len <= SUBMAP_MAX_POINTS:
+        raise ValueError(f"drive_rows: max_len={max_len} outside 1 .. 2^20")
+    if not 0 <= out_rows < 1 << 31:
+        raise ValueError(f"drive_rows: {out_rows} output rows; fewer than 2^31")
+    if out is None:
+        out = torch.empty((max(out_rows, 1), 3), dtype=torch.float32, device=points.device)[:out_rows]
+    else:
+        _req(out, "out")
+        if out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < out_rows or not out.is_contiguous():
+            raise ValueError(f"drive_rows: out must be a contiguous [>= {out_rows}, 3] tensor, got {tuple(out.shape)}")
+    if out_rows:
+        _call("drive_rows", _lib.load().lpd_drive_rows, _ptr(points), ld, points.shape[0], _ptr(offsets), _ptr(poses), S, _ptr(plan.contiguous()), W,
+              _ptr(out_off.contiguous()), int(frame), max_len, _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
