@@ -647,6 +647,47 @@ int lpd_drive_plan(const long long* D, int S, const int32_t* offsets, const doub
 int lpd_drive_rows(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, const int32_t* plan, int W,
                    const int32_t* out_off, int frame, int max_len, float* out, void* stream);
 
+/*
+ * Geometric verification of retrieved places (csrc/lpd_align.hip; arithmetic in csrc/lpd_align_math.h): correlative scan matching
+ * (Olson, "Real-time correlative scan matching", ICRA 2009) of (query, candidate) submap pairs.  Both clouds are rasterised into
+ * bird's-eye occupancy bitmaps with a few height layers; yaw is searched over a caller-made table and a window of cell shifts is
+ * searched exhaustively; the score is a popcount of ANDed bitmaps.  The step behind lpd_recall_pairs' topk_idx / lpd_retrieval_topk:
+ * which candidate is geometrically the same place, and the relative pose to it.  This comment is the specification, and
+ * lpd_align_math.h settles every detail it leaves open.  Integer-only once the cells are assigned; no initial guess; no read-back.
+ *   A        [TA][N][3] fp32; may be the same table as B.  B [TB][N][3] fp32.  1 <= N <= 16384.  NaN and inf allowed (no bit is set).
+ *   scaleA   [TA] fp32 metres per unit (Submaps.scale), or NULL for 1.0f; scaleB [TB] alike
+ *   pairs    [P][2] int32 = (row of A, row of B), 1 <= P <= 2^20.  A pair that names a row outside its table is NEVER READ: its best is
+ *            (-1, 0, 0, 0, 0, 0, 0, 0) and its yaw_scores are 0.
+ *   rot      [R][2] fp32 = (cos, sin), the CALLER's table (made once on the host): no trigonometric function is evaluated on the device.
+ *            Pair p uses the entries rot[(first[p] + h) mod R] (the non-negative remainder), h = 0 .. H-1; first [P] int32, or NULL for 0.
+ *            1 <= H <= R <= 8192, H <= 1024.  The integer indirection lets a coarse-to-fine chain stay on the device, bit-exact.
+ *   t0       [P][2] fp32 metres: a pre-translation of A, or NULL
+ * fp32, every operation rounded once, no contraction, every comparison false on NaN.  For a point (x, y, z) of cloud i and (c, s):
+ *  1 Scale.    p = (x*sc, y*sc, z*sc), sc = scale[i] or 1.0f.
+ *  2 Rotate (A only).  xr = (px*c) - (py*s),  yr = (px*s) + (py*c);  then xr = xr + t0x, yr = yr + t0y when t0 is given.  B: xr = px,
+ *              yr = py.
+ *  3 Cell.     fx = floorf(xr * inv_cell) + 64.0f, valid iff fx >= 0.0f && fx < 128.0f, ix = (int) fx only after that test; iy alike;
+ *              fz = floorf((pz - z0) * inv_zcell), valid iff 0 <= fz < layers.  A point with any invalid index, or any non-finite
+ *              coordinate, sets no bit.
+ *  4 Bitmap.   occ[layer][iy] is a 128-bit row, bit ix set.  The grid is fixed at 128 x 128 cells; layers 1 .. 4.
+ *  5 Score.    score(h, dy, dx) = sum over layers and rows iy of popcount(shift(occA_h[l][iy], dx) & occB[l][iy + dy]);  shift moves
+ *              bit ix to ix + dx, bits that leave [0, 128) are dropped; rows with iy + dy outside [0, 128) are dropped.
+ *              dy, dx in [-S, S], 0 <= S <= 16.
+ *  6 Winner.   The largest score; ties to the smallest (h, dy, dx) in lexicographic order, dy and dx counted from -S.
+ *  7 Meaning.  p_B ~ R(yaw_h) p_A + t0 + (dx, dy) * cell, with cell = 1 / inv_cell.
+ * best [P][8] int32 = (h, dy, dx, score, nA, nB, 1, 0): nA = the occupied cells of A at the winning yaw, nB = the occupied cells of B.
+ * yaw_scores [P][H] int32, or NULL: the maximum over the shifts for every hypothesis.  inv_cell, inv_zcell finite and > 0, z0 finite.
+ * ws = lpd_align_workspace_bytes(P, H) bytes (may be 0: then ws may be NULL), 16-byte aligned, the caller's, one per call in flight, no
+ * state between calls: for a small P the hypotheses of a pair are spread over several workgroups, whose packed (score, inverted
+ * candidate number) keys are combined by an integer maximum in a fixed order.  No float atomics; integer LDS atomics only: the same
+ * bits in every launch and in any thread order.
+ */
+long long lpd_align_workspace_bytes(int P, int H);
+int lpd_align_pairs(const float* A, int TA, const float* scaleA, const float* B, int TB, const float* scaleB, int N,
+                    const int32_t* pairs, int P, const float* rot, int R, const int32_t* first, int H, const float* t0,
+                    float inv_cell, int S, float z0, float inv_zcell, int layers,
+                    int32_t* best, int32_t* yaw_scores, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

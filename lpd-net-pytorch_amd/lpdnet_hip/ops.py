@@ -1539,6 +1539,87 @@ def drive_rows(points, offsets, poses, plan, out_off, max_len, out_rows, frame=1
 
 
 # ------------------------------------------------------------------------------------------------
+# geometric verification of retrieved places (csrc/lpd_align.hip)
+# ------------------------------------------------------------------------------------------------
+ALIGN_GRID, ALIGN_MAX_S, ALIGN_MAX_LAYERS, ALIGN_MAX_H, ALIGN_MAX_R = 128, 16, 4, 1024, 8192      # csrc/lpd_align_math.h
+ALIGN_MAX_POINTS, ALIGN_MAX_PAIRS = 16384, 1 << 20
+
+
+def _align_arg(t, name, dtype, optional=False):
+    """type and dtype of an argument of align_pairs, BEFORE its device: the host-side validation reads no device"""
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"align_pairs: {name}: expected a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"align_pairs: {name}: expected {dtype}, got {t.dtype}")
+
+
+def _align_table(t, name):
+    """[T, N, 3] or [T, 1, N, 3] fp32 -> the [T, N, 3] view"""
+    _align_arg(t, name, torch.float32)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or not 1 <= t.shape[1] <= ALIGN_MAX_POINTS:
+        raise ValueError(f"align_pairs: {name} must be [T, N, 3] or [T, 1, N, 3] with T >= 1 and 1 <= N <= {ALIGN_MAX_POINTS}, got {tuple(t.shape)}")
+    return t
+
+
+def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a=None, scale_b=None, first=None, t0=None, want_yaw_scores=True):
+    """Correlative scan matching of P (row of a, row of b) pairs over H yaw hypotheses and (2S+1)^2 cell shifts (lpd_align_pairs;
+    definition in include/lpd_hip.h).  a [TA, N, 3], b [TB, N, 3] fp32 (or [T, 1, N, 3]; may be one tensor), pairs [P, 2] int32, rot
+    [R, 2] fp32 = the caller's (cos, sin) table, first [P] int32 or None, t0 [P, 2] fp32 metres or None, scale_a [TA] / scale_b [TB]
+    fp32 metres per unit or None -- all on the device.  -> (best [P, 8] int32 = (h, dy, dx, score, nA, nB, 1, 0), yaw_scores [P, H]
+    int32 or None).  Nothing is read back."""
+    a, b = _align_table(a, "a"), _align_table(b, "b")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"align_pairs: a and b hold {a.shape[1]} and {b.shape[1]} points a cloud; one N")
+    TA, N, TB = a.shape[0], a.shape[1], b.shape[0]
+    _align_arg(pairs, "pairs", torch.int32)
+    _align_arg(rot, "rot", torch.float32)
+    _align_arg(scale_a, "scale_a", torch.float32, True)
+    _align_arg(scale_b, "scale_b", torch.float32, True)
+    _align_arg(first, "first", torch.int32, True)
+    _align_arg(t0, "t0", torch.float32, True)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= ALIGN_MAX_PAIRS:
+        raise ValueError(f"align_pairs: pairs must be [P, 2] with 1 <= P <= 2^20, got {tuple(pairs.shape)}")
+    P = pairs.shape[0]
+    if rot.dim() != 2 or rot.shape[1] != 2 or not 1 <= rot.shape[0] <= ALIGN_MAX_R:
+        raise ValueError(f"align_pairs: rot must be [R, 2] with 1 <= R <= {ALIGN_MAX_R}, got {tuple(rot.shape)}")
+    R = rot.shape[0]
+    H, S, layers = int(H), int(S), int(layers)
+    if not (1 <= H <= R and H <= ALIGN_MAX_H):
+        raise ValueError(f"align_pairs: H={H} (1 <= H <= R = {R}, H <= {ALIGN_MAX_H})")
+    if not 0 <= S <= ALIGN_MAX_S:
+        raise ValueError(f"align_pairs: S={S} outside 0 .. {ALIGN_MAX_S}")
+    if not 1 <= layers <= ALIGN_MAX_LAYERS:
+        raise ValueError(f"align_pairs: layers={layers} outside 1 .. {ALIGN_MAX_LAYERS}")
+    inv_cell, z0, inv_zcell = float(inv_cell), float(z0), float(inv_zcell)
+    if not (0.0 < inv_cell < float("inf") and 0.0 < inv_zcell < float("inf") and abs(z0) < float("inf")):
+        raise ValueError(f"align_pairs: inv_cell={inv_cell} inv_zcell={inv_zcell} (finite, > 0) z0={z0} (finite)")
+    if scale_a is not None and tuple(scale_a.shape) != (TA,) or scale_b is not None and tuple(scale_b.shape) != (TB,):
+        raise ValueError(f"align_pairs: scale_a / scale_b must be [TA] = ({TA},) / [TB] = ({TB},)")
+    if first is not None and tuple(first.shape) != (P,):
+        raise ValueError(f"align_pairs: first must be [P] = ({P},), got {tuple(first.shape)}")
+    if t0 is not None and tuple(t0.shape) != (P, 2):
+        raise ValueError(f"align_pairs: t0 must be [P, 2] = ({P}, 2), got {tuple(t0.shape)}")
+    for t, name in ((a, "a"), (b, "b"), (pairs, "pairs"), (rot, "rot"), (scale_a, "scale_a"), (scale_b, "scale_b"), (first, "first"), (t0, "t0")):
+        _req(t, name, None if t is None else t.dtype)      # the device: no CPU path
+        if t is not None and t.device != a.device:
+            raise ValueError(f"align_pairs: {name} is on {t.device}, a on {a.device}")
+    a, b = a.contiguous(), b.contiguous()
+    lib = _lib.load()
+    best = torch.empty((P, 8), dtype=torch.int32, device=a.device)
+    yaw_scores = torch.empty((P, H), dtype=torch.int32, device=a.device) if want_yaw_scores else None
+    ws = torch.empty((max(int(lib.lpd_align_workspace_bytes(P, H)), 16),), dtype=torch.uint8, device=a.device)
+    _call("align_pairs", lib.lpd_align_pairs, _ptr(a), TA, _ptr(None if scale_a is None else scale_a.contiguous()), _ptr(b), TB,
+          _ptr(None if scale_b is None else scale_b.contiguous()), N, _ptr(pairs.contiguous()), P, _ptr(rot.contiguous()), R,
+          _ptr(None if first is None else first.contiguous()), H, _ptr(None if t0 is None else t0.contiguous()), inv_cell, S, z0, inv_zcell,
+          layers, _ptr(best), _ptr(yaw_scores), _ptr(ws), _stream())
+    return best, yaw_scores
+
+
+# ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
 class BNStats:
