@@ -688,6 +688,54 @@ int lpd_align_pairs(const float* A, int TA, const float* scaleA, const float* B,
                     float inv_cell, int S, float z0, float inv_zcell, int layers,
                     int32_t* best, int32_t* yaw_scores, void* ws, void* stream);
 
+/*
+ * Refinement of a verified match to a full 6-DoF pose (csrc/lpd_icp.hip; arithmetic in csrc/lpd_icp_math.h): trimmed point-to-plane
+ * ICP (Chen and Medioni 1992; the linearised form of Low 2004) of (query, candidate) pairs, started from the yaw and shift of
+ * lpd_align_pairs, and the normals it needs.  The step behind lpd_align_pairs: roll, pitch and z, and a measure of how well the
+ * clouds fit.  This comment is the specification, and lpd_icp_math.h settles every detail it leaves open.  fp32 unless stated, every
+ * operation rounded once, nothing contracted, every comparison false on NaN, dot products ((a0*b0) + (a1*b1)) + (a2*b2).
+ *
+ * lpd_point_normals: unit normals of a cloud's points from its kNN lists.
+ *   xyz [B*N][ldx], idx [B][N][K] as for lpd_local_features, its rule for an index outside the cloud included (the cloud's last point
+ *   is read instead); 4 <= K <= 64, K <= N.  The moments and the covariance are lpd_feat_add / lpd_feat_cov over the K entries, centred
+ *   on the query point; the eigenvectors come from lpd_feat_math.h's six Jacobi sweeps carrying all three rows of V.
+ *   normals [B*N][3] = the unit eigenvector of the smallest eigenvalue, normalised once more in fp32; its sign is what the sweeps give.
+ *   (0, 0, 0) when the neighbourhood has no extent (l1 == 0) or a moment is not finite: "this point takes no part" downstream.
+ *   flatness [B*N] or NULL = l3 / l2, 0 where l2 == 0 or the normal is 0.  Clouds of N <= 4096 are staged in LDS, larger ones are read
+ *   through L2 (LPD_DEBUG=normals-l2 sends every cloud that way): the same bits.
+ *
+ * lpd_icp_pairs.
+ *   A, B, scaleA, scaleB, pairs: exactly those of lpd_align_pairs; a pair that names a row outside its table is NEVER READ.
+ *   1 <= N <= 16384, 1 <= P <= 2^20.  normalsB [TB][N][3].
+ *   pose     [P][12] float64, IN and OUT: the top three rows of the homogeneous matrix, row-major (R | t), the layout of lpd_drive_*'s
+ *            poses: p_B ~ R p_A + t in the clouds' scaled (metric, centred) frames.
+ *   dmax     HOST array of iters + 1 fp32 distances, read by the call; every entry finite, > 0 and <= 16.  0 <= iters <= 64.
+ *            6 <= min_inliers.
+ * iters + 1 passes; pass s is computed at the pose that pass s - 1 left:
+ *  1 Transform.  (M, u) = the pose rounded to fp32 once; a = (x*sc, y*sc, z*sc); p_c = (((M_c0*a_x) + (M_c1*a_y)) + (M_c2*a_z)) + u_c.
+ *              A point with a non-finite p or any |p_c| > 512 has no correspondence.
+ *  2 Correspondence.  q_j = B's point j scaled; d = q_j - p, d2_j = ((dx*dx) + (dy*dy)) + (dz*dz); j* = the j with the smallest d2,
+ *              ties to the lowest j, a non-finite q_j never wins.  The correspondence is j* iff d2_{j*} <= dmax_s * dmax_s (one
+ *              product) and normalsB[j*] is not (0, 0, 0); otherwise there is none.  Only this outcome is specified.
+ *  3 Sums.     e = q - p, r = ((e_x*n_x) + (e_y*n_y)) + (e_z*n_z), c = p x n (each component (p_y*n_z) - (p_z*n_y) and so on),
+ *              J = (c, n); Ji = (int64) rint(J * 1024) clamped to +-2^20, half to even, ri alike.  32 int64 per (pass, pair):
+ *              [0] m, [1..21] sum Ji_a Ji_b for a <= b (row-major), [22..27] sum Ji_a ri, [28] sum ri ri, [29..31] 0.  Exact in any order.
+ *  4 Step (passes 0 .. iters-1), float64, in the order written in lpd_icp_solve: H x = g by an unpivoted LDL^T.  Refused -- the pose
+ *              stays bit for bit -- when m < min_inliers or a pivot is not positive and finite (or x or the new pose is not finite).
+ *              Otherwise w = x[0..2], dt = x[3..5], dR = the rotation of the unit quaternion (1, w/2) / |(1, w/2)| (+, -, *, /, sqrt
+ *              only), R <- dR R, t <- dR t + dt.
+ * sums [iters+1][P][32] int64 receives every pass's sums; nn [P][N] int32, or NULL: the LAST pass's correspondence of every point of
+ * A, or -1; info [P][4] int32 = (1 for a valid pair else -1, steps applied, steps refused, correspondences of the last pass).  An
+ * invalid pair's pose is left as it is, its sums are 0 and its nn row -1.  ws = lpd_icp_workspace_bytes(P, N, iters) bytes (0: bad
+ * dims), 16-byte aligned, the caller's, one per call in flight, no state between calls.  Integer atomics only: the same bits in every
+ * launch.  Every call only enqueues.
+ */
+long long lpd_icp_workspace_bytes(int P, int N, int iters);
+int lpd_point_normals(const float* xyz, int ldx, const int32_t* idx, int B, int N, int K, float* normals, float* flatness, void* stream);
+int lpd_icp_pairs(const float* A, int TA, const float* scaleA, const float* B, int TB, const float* scaleB, const float* normalsB, int N,
+                  const int32_t* pairs, int P, const float* dmax, int iters, int min_inliers, double* pose, int32_t* info,
+                  long long* sums, int32_t* nn, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -1545,23 +1545,23 @@ ALIGN_GRID, ALIGN_MAX_S, ALIGN_MAX_LAYERS, ALIGN_MAX_H, ALIGN_MAX_R = 128, 16, 4
 ALIGN_MAX_POINTS, ALIGN_MAX_PAIRS = 16384, 1 << 20
 
 
-def _align_arg(t, name, dtype, optional=False):
+def _align_arg(t, name, dtype, optional=False, what="align_pairs"):
     """type and dtype of an argument of align_pairs, BEFORE its device: the host-side validation reads no device"""
     if t is None and optional:
         return
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"align_pairs: {name}: expected a tensor")
+        raise TypeError(f"{what}: {name}: expected a tensor")
     if t.dtype != dtype:
-        raise TypeError(f"align_pairs: {name}: expected {dtype}, got {t.dtype}")
+        raise TypeError(f"{what}: {name}: expected {dtype}, got {t.dtype}")
 
 
-def _align_table(t, name):
+def _align_table(t, name, what="align_pairs"):
     """[T, N, 3] or [T, 1, N, 3] fp32 -> the [T, N, 3] view"""
-    _align_arg(t, name, torch.float32)
+    _align_arg(t, name, torch.float32, what=what)
     if t.dim() == 4 and t.shape[1] == 1:
         t = t[:, 0]
     if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or not 1 <= t.shape[1] <= ALIGN_MAX_POINTS:
-        raise ValueError(f"align_pairs: {name} must be [T, N, 3] or [T, 1, N, 3] with T >= 1 and 1 <= N <= {ALIGN_MAX_POINTS}, got {tuple(t.shape)}")
+        raise ValueError(f"{what}: {name} must be [T, N, 3] or [T, 1, N, 3] with T >= 1 and 1 <= N <= {ALIGN_MAX_POINTS}, got {tuple(t.shape)}")
     return t
 
 
@@ -1617,6 +1617,116 @@ def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a
           _ptr(None if first is None else first.contiguous()), H, _ptr(None if t0 is None else t0.contiguous()), inv_cell, S, z0, inv_zcell,
           layers, _ptr(best), _ptr(yaw_scores), _ptr(ws), _stream())
     return best, yaw_scores
+
+
+# ------------------------------------------------------------------------------------------------
+# refinement of a verified match to a 6-DoF pose (csrc/lpd_icp.hip)
+# ------------------------------------------------------------------------------------------------
+ICP_MAX_POINTS, ICP_MAX_PAIRS, ICP_MAX_ITERS, ICP_MIN_INLIERS, ICP_MAX_DMAX, ICP_SUMS = 16384, 1 << 20, 64, 6, 16.0, 32      # csrc/lpd_icp_math.h
+
+
+def _icp_arg(what, t, name, dtype, optional=False):
+    _align_arg(t, name, dtype, optional, what)
+
+
+def _icp_devices(what, first, named):
+    for t, name in named:
+        _req(t, name, None if t is None else t.dtype)      # the device: no CPU path
+        if t is not None and t.device != first.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, {named[0][1]} on {first.device}")
+
+
+def point_normals(xyz_rows, idx, B, N, want_flatness=False):
+    """Unit normals of every point from its kNN list (lpd_point_normals; definition in include/lpd_hip.h).  xyz_rows [B*N, >= 3] fp32
+    point-major, idx [B, N, K] int32 (knn_pm), 4 <= K <= 64, K <= N -> normals [B*N, 3] fp32, (0, 0, 0) where a neighbourhood has no
+    extent or is not finite; with want_flatness also l3 / l2 [B*N] fp32.  Nothing is read back."""
+    what = "point_normals"
+    _icp_arg(what, xyz_rows, "xyz_rows", torch.float32)
+    _icp_arg(what, idx, "idx", torch.int32)
+    B, N = int(B), int(N)
+    if B < 1 or N < 1 or B * N >= 1 << 31:
+        raise ValueError(f"point_normals: B={B} N={N} (>= 1, B * N < 2^31)")
+    if xyz_rows.dim() != 2 or xyz_rows.shape[0] != B * N or xyz_rows.shape[1] < 3 or xyz_rows.stride(1) != 1:
+        raise ValueError(f"point_normals: xyz_rows must be [B*N, >= 3] with contiguous rows, got {tuple(xyz_rows.shape)}")
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] != N:
+        raise ValueError(f"point_normals: idx must be [B, N, K], got {tuple(idx.shape)}")
+    K = idx.shape[2]
+    if not (4 <= K <= 64 and K <= N):
+        raise ValueError(f"point_normals: need 4 <= K <= 64 and K <= N (K={K} N={N})")
+    _icp_devices(what, xyz_rows, ((xyz_rows, "xyz_rows"), (idx, "idx")))
+    idx = idx.contiguous()
+    lib = _lib.load()
+    normals = torch.empty((B * N, 3), dtype=torch.float32, device=xyz_rows.device)
+    flat = torch.empty((B * N,), dtype=torch.float32, device=xyz_rows.device) if want_flatness else None
+    _call(f"point_normals[k={K}]", lib.lpd_point_normals, _ptr(xyz_rows), xyz_rows.stride(0), _ptr(idx), B, N, K, _ptr(normals), _ptr(flat),
+          _stream())
+    return (normals, flat) if want_flatness else normals
+
+
+def icp_dmax(dmax, iters):
+    """the HOST array of iters + 1 fp32 distances of lpd_icp_pairs from a sequence: every entry finite, > 0 and <= 16"""
+    vals = [float(v) for v in dmax]
+    if len(vals) != iters + 1:
+        raise ValueError(f"icp_pairs: dmax holds {len(vals)} entries; iters + 1 = {iters + 1}")
+    for s, v in enumerate(vals):
+        if not 0.0 < v <= ICP_MAX_DMAX:      # false for NaN as well
+            raise ValueError(f"icp_pairs: dmax[{s}]={v!r} (finite, > 0, <= {ICP_MAX_DMAX})")
+    arr = (ctypes.c_float * (iters + 1))(*vals)
+    if any(not 0.0 < float(v) <= ICP_MAX_DMAX for v in arr):      # after the rounding to fp32
+        raise ValueError(f"icp_pairs: a dmax rounds to fp32 outside (0, {ICP_MAX_DMAX}]")
+    return arr
+
+
+def icp_pairs(a, b, normals_b, pairs, pose, dmax, min_inliers, scale_a=None, scale_b=None, want_nn=False):
+    """Trimmed point-to-plane ICP of P (row of a, row of b) pairs (lpd_icp_pairs; definition in include/lpd_hip.h).  a [TA, N, 3],
+    b [TB, N, 3] fp32 (or [T, 1, N, 3]; may be one tensor), normals_b [TB, N, 3] fp32 (point_normals), pairs [P, 2] int32, pose
+    [P, 12] float64 = the start (R | t) row-major (not written: the result is a new tensor), scale_a [TA] / scale_b [TB] fp32 or None
+    -- all on the device; dmax: iters + 1 distances in metres on the host, one a pass; min_inliers >= 6.
+    -> (pose [P, 12] float64, info [P, 4] int32 = (1 | -1, steps applied, steps refused, correspondences of the last pass),
+    sums [iters + 1, P, 32] int64, nn [P, N] int32 or None).  Nothing is read back."""
+    what = "icp_pairs"
+    a, b = _align_table(a, "a", what), _align_table(b, "b", what)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"icp_pairs: a and b hold {a.shape[1]} and {b.shape[1]} points a cloud; one N")
+    TA, N, TB = a.shape[0], a.shape[1], b.shape[0]
+    _icp_arg(what, normals_b, "normals_b", torch.float32)
+    _icp_arg(what, pairs, "pairs", torch.int32)
+    _icp_arg(what, pose, "pose", torch.float64)
+    _icp_arg(what, scale_a, "scale_a", torch.float32, True)
+    _icp_arg(what, scale_b, "scale_b", torch.float32, True)
+    if tuple(normals_b.shape) != (TB, N, 3):
+        raise ValueError(f"icp_pairs: normals_b must be [TB, N, 3] = ({TB}, {N}, 3), got {tuple(normals_b.shape)}")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= ICP_MAX_PAIRS:
+        raise ValueError(f"icp_pairs: pairs must be [P, 2] with 1 <= P <= 2^20, got {tuple(pairs.shape)}")
+    P = pairs.shape[0]
+    if tuple(pose.shape) != (P, 12):
+        raise ValueError(f"icp_pairs: pose must be [P, 12] = ({P}, 12), got {tuple(pose.shape)}")
+    if scale_a is not None and tuple(scale_a.shape) != (TA,) or scale_b is not None and tuple(scale_b.shape) != (TB,):
+        raise ValueError(f"icp_pairs: scale_a / scale_b must be [TA] = ({TA},) / [TB] = ({TB},)")
+    try:
+        iters = len(dmax) - 1
+    except TypeError:
+        raise TypeError("icp_pairs: dmax must be a sequence of iters + 1 distances") from None
+    if not 0 <= iters <= ICP_MAX_ITERS:
+        raise ValueError(f"icp_pairs: dmax holds {iters + 1} entries; iters + 1 lies in 1 .. {ICP_MAX_ITERS + 1}")
+    dm = icp_dmax(dmax, iters)
+    if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or not ICP_MIN_INLIERS <= int(min_inliers) < 1 << 31:
+        raise ValueError(f"icp_pairs: min_inliers={min_inliers!r} (an integer >= {ICP_MIN_INLIERS})")
+    min_inliers = int(min_inliers)
+    _icp_devices(what, a, ((a, "a"), (b, "b"), (normals_b, "normals_b"), (pairs, "pairs"), (pose, "pose"), (scale_a, "scale_a"),
+                           (scale_b, "scale_b")))
+    a, b = a.contiguous(), b.contiguous()
+    lib = _lib.load()
+    dev = a.device
+    pose = pose.contiguous().clone()
+    info = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    sums = torch.empty((iters + 1, P, ICP_SUMS), dtype=torch.int64, device=dev)
+    nn = torch.empty((P, N), dtype=torch.int32, device=dev) if want_nn else None
+    ws = torch.empty((max(int(lib.lpd_icp_workspace_bytes(P, N, iters)), 16),), dtype=torch.uint8, device=dev)
+    _call("icp_pairs", lib.lpd_icp_pairs, _ptr(a), TA, _ptr(None if scale_a is None else scale_a.contiguous()), _ptr(b), TB,
+          _ptr(None if scale_b is None else scale_b.contiguous()), _ptr(normals_b.contiguous()), N, _ptr(pairs.contiguous()), P, dm, iters,
+          min_inliers, _ptr(pose), _ptr(info), _ptr(sums), _ptr(nn), _ptr(ws), _stream())
+    return pose, info, sums, nn
 
 
 # ------------------------------------------------------------------------------------------------

@@ -3,12 +3,15 @@
 A descriptor ranks candidates; whether a candidate IS the query's place, and the relative pose to it (the loop-closure constraint a
 mapper needs), is a question about the two clouds.  This module answers it without copying a cloud back: correlative scan matching
 (csrc/lpd_align.hip; the definition is in include/lpd_hip.h) of bird's-eye occupancy bitmaps over every yaw and a window of cell
-shifts, then a second, finer pass through the same kernel around the coarse winner.
+shifts, then a second, finer pass through the same kernel around the coarse winner; and, from that yaw and shift, trimmed
+point-to-plane ICP (csrc/lpd_icp.hip) to the full rigid transform with a measure of how well the clouds fit.
 
     al = verify.align_pairs(sub_q, sub_db, pairs)                  # Submaps (scale and centre taken from them) or [T, N, 3] tensors
     al.yaw, al.translation, al.overlap, al.matrix()                # [P], [P, 2] metres, [P], [P, 4, 4]: A's metric frame -> B's
     v = verify.verify_candidates(sub_q, sub_db, topk_idx, min_overlap=0.3)
     v.order, v.accepted, v.overlap                                 # [Q, K]: the ranks re-sorted by score, the accepted candidates
+    rf = verify.refine_pairs(sub_q, sub_db, pairs, init=al)        # 6-DoF: rf.pose [P, 3, 4], rf.inlier_share, rf.rms, rf.matrix()
+    v = verify.refine_candidates(sub_q, sub_db, topk_idx, min_overlap=0.3)      # verify_candidates + v.refinement, shaped [Q, K]
 
 Integer-only once the cells are assigned: the same bits in every launch, and equal to the numpy restatement (tests/align_ref.py).  The
 (cos, sin) tables are made once on the host in float64 and rounded to fp32; the fine pass takes a window of the dense table by an
@@ -207,14 +210,197 @@ def align_pairs(a, b, pairs, search=AlignSearch(), scale_a=None, scale_b=None, c
                      valid=valid, coarse=coarse, fine=fine, center_a=centre(center_a, 0, TA), center_b=centre(center_b, 1, TB))
 
 
-class Verification:
-    """What verify_candidates returns: every field of Alignment shaped [Q, K] (translation [Q, K, 2], matrix() [Q, K, 4, 4]), plus
-    order [Q, K] int64 = the ranks 0 .. K-1 of every query re-sorted by descending score (ties keep the retrieval order, skipped
-    entries come last) and accepted [Q, K] bool (valid and overlap >= min_overlap), or None when no min_overlap was given."""
-    __slots__ = ("alignment", "order", "accepted")
+class RefineSearch:
+    """The search of refine_pairs, validated and frozen.  k: neighbours a normal of b is made from (4 .. 64); dmax: the trimming
+    distance in metres, one number or a sequence of `iterations` numbers, one a pass; iterations: steps (0 .. 64); min_inliers: a
+    step with fewer correspondences is refused (>= 6); final_dmax: the distance of the pass behind the last step, which makes
+    inliers and rms (None: the last entry of dmax)."""
+    __slots__ = ("k", "dmax", "iterations", "min_inliers", "final_dmax")
 
-    def __init__(self, alignment, order, accepted):
-        self.alignment, self.order, self.accepted = alignment, order, accepted
+    def __init__(self, k=16, dmax=1.0, iterations=8, min_inliers=32, final_dmax=None):
+        def whole(v, name, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"RefineSearch: {name}={v!r} (an integer in {lo} .. {hi})")
+            return int(v)
+
+        def dist(v, name):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"RefineSearch: {name}={v!r} (a number)")
+            v = float(v)
+            if not (0.0 < v <= ops.ICP_MAX_DMAX and 0.0 < float(np.float32(v)) <= ops.ICP_MAX_DMAX):      # false for NaN
+                raise ValueError(f"RefineSearch: {name}={v!r} (finite, > 0, <= {ops.ICP_MAX_DMAX})")
+            return v
+        set_ = object.__setattr__
+        set_(self, "k", whole(k, "k", 4, 64))
+        set_(self, "iterations", whole(iterations, "iterations", 0, ops.ICP_MAX_ITERS))
+        set_(self, "min_inliers", whole(min_inliers, "min_inliers", ops.ICP_MIN_INLIERS, (1 << 31) - 1))
+        if isinstance(dmax, (list, tuple, np.ndarray)):
+            if len(dmax) != self.iterations:
+                raise ValueError(f"RefineSearch: dmax holds {len(dmax)} entries; iterations = {self.iterations}")
+            sched = tuple(dist(v, f"dmax[{i}]") for i, v in enumerate(dmax))
+        else:
+            sched = (dist(dmax, "dmax"),) * self.iterations
+        if final_dmax is None:
+            if not sched:
+                if isinstance(dmax, (list, tuple, np.ndarray)):
+                    raise ValueError("RefineSearch: iterations = 0 with an empty dmax needs a final_dmax")
+                final_dmax = dmax
+            else:
+                final_dmax = sched[-1]
+        set_(self, "dmax", sched)
+        set_(self, "final_dmax", dist(final_dmax, "final_dmax"))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("RefineSearch is frozen")
+
+    def __delattr__(self, name):
+        raise AttributeError("RefineSearch is frozen")
+
+    def __repr__(self):
+        return "RefineSearch(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+    def __eq__(self, other):
+        return isinstance(other, RefineSearch) and all(getattr(self, n) == getattr(other, n) for n in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, n) for n in self.__slots__))
+
+    @property
+    def schedule(self):
+        """the iterations + 1 distances of lpd_icp_pairs"""
+        return self.dmax + (self.final_dmax,)
+
+
+class Refinement:
+    """What refine_pairs returns, one entry per pair (leading shape [P], or [Q, K] from refine_candidates): pose [.., 3, 4] float64 =
+    (R | t), p_B ~ R p_A + t in the clouds' centred metric frames; valid bool (False: the pair names a row outside its table, or its
+    alignment was not valid; its pose is the start); steps, refused int32 = the steps applied and refused; inliers int32 = the
+    correspondences of the last pass, inlier_share = inliers / N; rms float64 metres = sqrt(sum ri^2 / m) / 1024 of the last pass, 0
+    where m = 0; sums [.., iterations + 1, 32] int64 = every pass's sums; nn [.., N] int32 or None; center_a / center_b [.., 3]
+    float64 or None."""
+    __slots__ = ("pose", "valid", "steps", "refused", "inliers", "inlier_share", "rms", "sums", "nn", "center_a", "center_b")
+
+    def __init__(self, **kw):
+        for n in self.__slots__:
+            setattr(self, n, kw[n])
+
+    def matrix(self):
+        """[.., 4, 4] float64 taking A's metric frame into B's.  With centres p_B = R (p_A - c_A) + t + c_B, as Alignment.matrix()."""
+        M = torch.zeros(tuple(self.pose.shape[:-2]) + (4, 4), dtype=torch.float64, device=self.pose.device)
+        M[..., :3, :] = self.pose
+        M[..., 3, 3] = 1.0
+        if self.center_a is not None:
+            M[..., :3, 3] -= (M[..., :3, :3] @ self.center_a[..., None])[..., 0]
+        if self.center_b is not None:
+            M[..., :3, 3] += self.center_b
+        return M
+
+    def _shaped(self, Q, K):
+        def v(t):
+            return None if t is None else t.reshape((Q, K) + tuple(t.shape[1:]))
+        return Refinement(**{n: v(getattr(self, n)) for n in self.__slots__})
+
+
+def point_normals(b, k=16):
+    """Unit normals [T, N, 3] fp32 of every point of b (a Submaps or a [T, N, 3] / [T, 1, N, 3] fp32 device tensor) from its k nearest
+    neighbours (ops.knn_pm, then ops.point_normals); (0, 0, 0) where a neighbourhood has no extent or is not finite."""
+    from . import submap
+    x = b.x if isinstance(b, submap.Submaps) else b
+    x = ops._align_table(x, "b", "point_normals")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 4 <= int(k) <= 64 or int(k) > x.shape[1]:
+        raise ValueError(f"point_normals: k={k!r} (an integer in 4 .. 64, at most N = {x.shape[1]})")
+    ops._req(x, "b")
+    T, N = x.shape[0], x.shape[1]
+    rows = x.contiguous().reshape(T * N, 3)
+    idx = ops.knn_pm(rows, T, N, int(k))
+    return ops.point_normals(rows, idx, T, N).reshape(T, N, 3)
+
+
+def _check_init(init, P):
+    """type and shape of refine_pairs' `init`, before any device is looked at"""
+    if init is None:
+        return
+    if isinstance(init, Alignment):
+        if tuple(init.yaw.shape) != (P,):
+            raise ValueError(f"refine_pairs: init is an Alignment of {tuple(init.yaw.shape)} pairs; pairs holds {P}")
+        return
+    if not isinstance(init, torch.Tensor) or init.dtype != torch.float64:
+        raise TypeError("refine_pairs: init must be an Alignment, a float64 tensor or None")
+    if tuple(init.shape) not in ((P, 12), (P, 3, 4), (P, 4, 4)):
+        raise ValueError(f"refine_pairs: init must be [P, 12], [P, 3, 4] or [P, 4, 4] with P = {P}, got {tuple(init.shape)}")
+
+
+def _init_pose(init, P, dev):
+    """-> (pose [P, 12] float64, ok [P] bool or None) of refine_pairs' `init`"""
+    if init is None:
+        return torch.eye(3, 4, dtype=torch.float64, device=dev).reshape(1, 12).repeat(P, 1), None
+    if isinstance(init, Alignment):
+        c, s = torch.cos(init.yaw), torch.sin(init.yaw)
+        M = torch.zeros((P, 3, 4), dtype=torch.float64, device=dev)
+        M[:, 0, 0], M[:, 0, 1], M[:, 1, 0], M[:, 1, 1] = c, -s, s, c
+        M[:, 2, 2] = 1.0
+        M[:, 0, 3], M[:, 1, 3] = init.translation[:, 0], init.translation[:, 1]
+        return M.reshape(P, 12), init.valid
+    ops._req(init, "init", torch.float64)
+    if init.dim() == 3 and init.shape[1] == 4:
+        init = init[:, :3, :]
+    return init.reshape(P, 12), None
+
+
+def refine_pairs(a, b, pairs, init=None, search=RefineSearch(), normals_b=None, want_nn=False, scale_a=None, scale_b=None, center_a=None,
+                 center_b=None):
+    """Refine P (row of a, row of b) pairs to a full rigid transform by trimmed point-to-plane ICP (ops.icp_pairs).  a, b, pairs and the
+    scale / centre arguments are those of align_pairs.  init: the start -- an Alignment of the same pairs (the pose is made from its
+    yaw and translation on the device; a pair whose alignment is not valid is not read), a [P, 12], [P, 3, 4] or [P, 4, 4] float64
+    tensor, or None for the identity.  normals_b [T, N, 3]: the normals of b's clouds when the caller has them (point_normals), made
+    here otherwise.  -> Refinement.  Nothing is read back."""
+    if not isinstance(search, RefineSearch):
+        raise TypeError(f"refine_pairs: search must be a RefineSearch, got {type(search).__name__}")
+    a, scale_a, center_a = _cloud_args(a, scale_a, center_a, "a")
+    b, scale_b, center_b = _cloud_args(b, scale_b, center_b, "b")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype not in (torch.int32, torch.int64):
+        raise TypeError("refine_pairs: pairs must be an int32 or int64 tensor")
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"refine_pairs: pairs must be [P, 2], got {tuple(pairs.shape)}")
+    a3, b3 = ops._align_table(a, "a", "refine_pairs"), ops._align_table(b, "b", "refine_pairs")
+    TA, TB, N, P = a3.shape[0], b3.shape[0], a3.shape[1], pairs.shape[0]
+    _check_init(init, P)
+    ops._req(a3, "a")
+    dev = a3.device
+    if pairs.dtype == torch.int64:      # a row number beyond int32 is outside every table: it becomes -1, "not read"
+        pairs = torch.where((pairs >= 0) & (pairs < (1 << 31) - 1), pairs, torch.full_like(pairs, -1)).to(torch.int32)
+    pose0, ok = _init_pose(init, P, dev)
+    if ok is not None:
+        pairs = torch.where(ok[:, None], pairs, torch.full_like(pairs, -1))
+    if normals_b is None:
+        normals_b = point_normals(b3, min(search.k, N)) if N >= 4 else torch.zeros((TB, N, 3), dtype=torch.float32, device=dev)
+    pose, info, sums, nn = ops.icp_pairs(a3, b3, normals_b, pairs, pose0, search.schedule, search.min_inliers, scale_a=scale_a,
+                                         scale_b=scale_b, want_nn=want_nn)
+    valid = info[:, 0] == 1
+    last = sums[-1]
+    m = last[:, 0]
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    rms = torch.where(m > 0, torch.sqrt(last[:, 28].to(torch.float64) / m.clamp(min=1).to(torch.float64)) / 1024.0, zero)
+
+    def centre(c, col, T):
+        if c is None:
+            return None
+        rows = pairs[:, col].to(torch.int64).clamp(0, T - 1)
+        return torch.where(valid[:, None], c.to(device=dev, dtype=torch.float64)[rows], zero)
+    return Refinement(pose=pose.reshape(P, 3, 4), valid=valid, steps=info[:, 1], refused=info[:, 2], inliers=info[:, 3],
+                      inlier_share=info[:, 3].to(torch.float64) / float(N), rms=rms, sums=sums.permute(1, 0, 2), nn=nn,
+                      center_a=centre(center_a, 0, TA), center_b=centre(center_b, 1, TB))
+
+
+class Verification:
+    """What verify_candidates and refine_candidates return: every field of Alignment shaped [Q, K] (translation [Q, K, 2], matrix() [Q, K, 4, 4]), plus
+    order [Q, K] int64 = the ranks 0 .. K-1 of every query re-sorted by descending score (ties keep the retrieval order, skipped
+    entries come last) and accepted [Q, K] bool (valid and overlap >= min_overlap), or None when no min_overlap was given.
+    refinement: refine_candidates' Refinement of every pair from its alignment, shaped [Q, K]; None from verify_candidates."""
+    __slots__ = ("alignment", "order", "accepted", "refinement")
+
+    def __init__(self, alignment, order, accepted, refinement=None):
+        self.alignment, self.order, self.accepted, self.refinement = alignment, order, accepted, refinement
 
     def __getattr__(self, name):
         if name in Alignment.__slots__ or name == "matrix":
@@ -222,23 +408,38 @@ class Verification:
         raise AttributeError(name)
 
 
+def _verify(what, query, database, topk_idx, search, min_overlap, refine):
+    if not isinstance(topk_idx, torch.Tensor) or topk_idx.dtype not in (torch.int32, torch.int64) or topk_idx.dim() != 2:
+        raise TypeError(f"{what}: topk_idx must be a [Q, K] int32 or int64 tensor")
+    if min_overlap is not None:
+        min_overlap = float(min_overlap)
+        if not 0.0 <= min_overlap <= 1.0:
+            raise ValueError(f"{what}: min_overlap={min_overlap} outside 0 .. 1")
+    Q, K = topk_idx.shape
+    if Q < 1 or K < 1:
+        raise ValueError(f"{what}: topk_idx must be [Q >= 1, K >= 1], got {tuple(topk_idx.shape)}")
+    rows = torch.arange(Q, device=topk_idx.device, dtype=topk_idx.dtype)[:, None].expand(Q, K)
+    pairs = torch.stack((torch.where(topk_idx >= 0, rows, torch.full_like(rows, -1)), topk_idx), dim=2).reshape(Q * K, 2)
+    flat = align_pairs(query, database, pairs, search)
+    refinement = None if refine is None else refine_pairs(query, database, pairs, init=flat, search=refine)._shaped(Q, K)
+    al = flat._shaped(Q, K)
+    rank_key = torch.where(al.valid, al.score, torch.full_like(al.score, -1))
+    order = torch.sort(rank_key, dim=1, descending=True, stable=True).indices
+    accepted = None if min_overlap is None else al.valid & (al.overlap >= min_overlap)
+    return Verification(al, order, accepted, refinement)
+
+
 def verify_candidates(query, database, topk_idx, search=AlignSearch(), min_overlap=None):
     """Align every (query i, database row topk_idx[i, r]) pair -- topk_idx [Q, K] as lpd_recall_pairs / lpd_retrieval_topk leave it on
     the device, entries -1 are skipped (never read) -- and re-rank the candidates by the score of the last pass.  query / database:
     Submaps or [T, N, 3] device tensors.  -> Verification.  Nothing is read back."""
-    if not isinstance(topk_idx, torch.Tensor) or topk_idx.dtype not in (torch.int32, torch.int64) or topk_idx.dim() != 2:
-        raise TypeError("verify_candidates: topk_idx must be a [Q, K] int32 or int64 tensor")
-    if min_overlap is not None:
-        min_overlap = float(min_overlap)
-        if not 0.0 <= min_overlap <= 1.0:
-            raise ValueError(f"verify_candidates: min_overlap={min_overlap} outside 0 .. 1")
-    Q, K = topk_idx.shape
-    if Q < 1 or K < 1:
-        raise ValueError(f"verify_candidates: topk_idx must be [Q >= 1, K >= 1], got {tuple(topk_idx.shape)}")
-    rows = torch.arange(Q, device=topk_idx.device, dtype=topk_idx.dtype)[:, None].expand(Q, K)
-    pairs = torch.stack((torch.where(topk_idx >= 0, rows, torch.full_like(rows, -1)), topk_idx), dim=2).reshape(Q * K, 2)
-    al = align_pairs(query, database, pairs, search)._shaped(Q, K)
-    rank_key = torch.where(al.valid, al.score, torch.full_like(al.score, -1))
-    order = torch.sort(rank_key, dim=1, descending=True, stable=True).indices
-    accepted = None if min_overlap is None else al.valid & (al.overlap >= min_overlap)
-    return Verification(al, order, accepted)
+    return _verify("verify_candidates", query, database, topk_idx, search, min_overlap, None)
+
+
+def refine_candidates(query, database, topk_idx, search=AlignSearch(), min_overlap=None, refine=RefineSearch()):
+    """verify_candidates, and every pair refined from its alignment to a full rigid transform (refine_pairs with `refine`, a
+    RefineSearch): the Verification carries .refinement, a Refinement shaped [Q, K]; everything else is what verify_candidates
+    returns for the same arguments.  Nothing is read back."""
+    if not isinstance(refine, RefineSearch):
+        raise TypeError(f"refine_candidates: refine must be a RefineSearch, got {type(refine).__name__}")
+    return _verify("refine_candidates", query, database, topk_idx, search, min_overlap, refine)
