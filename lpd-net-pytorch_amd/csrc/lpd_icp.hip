@@ -2,8 +2,8 @@
 // and trimmed point-to-plane ICP of (query, candidate) pairs (lpd_icp_pairs).  Definition: include/lpd_hip.h; arithmetic:
 // lpd_icp_math.h.  What stands between lpd_align_pairs' yaw and shift and a loop-closure constraint, without copying a cloud back.
 //
-// point_normals_kernel   one lane per point, the lane walks its list once (lpd_feat_add), then the three-row Jacobi.  The two forms
-//                        of the neighbour read are those of lpd_feat.hip: the cloud in LDS (N <= 4096, 48 KiB) or through L2.
+// point_normals_kernel   one lane per point, the lane walks its list once (lpd_list_walk.h, the walk of lpd_feat.hip: the cloud in
+//                        LDS or through L2) adding the moments (lpd_feat_add), then the three-row Jacobi.
 // icp_init_kernel        one thread per pair: the pair's validity, info = (1 | -1, 0, 0, 0) and the fp32 pose into ws.
 // icp_pass_kernel        THE HOT PATH: N x N distance evaluations per pair and pass, in the order the definition fixes (no MFMA: a
 //                        -2 a.b expansion loses the bits).  IC_T = 256 threads = 4 waves, one workgroup per (pair, chunk of IC_CHUNK =
@@ -26,49 +26,24 @@
 
 #include "lpd_common.h"
 #include "lpd_icp_math.h"
+#include "lpd_list_walk.h"
 
 namespace {
 
-constexpr int PN_LDS_MAX_N = 4096;      // 12 N bytes of LDS: 48 KiB
-constexpr int PN_T_LDS = 512, PN_T_L2 = 256;
-
 template <bool LDS>
-__global__ __launch_bounds__(LDS ? PN_T_LDS : PN_T_L2) void point_normals_kernel(const float* __restrict__ xyz, int ldx,
-                                                                                 const int32_t* __restrict__ idx, int N, int K,
-                                                                                 float* __restrict__ normals, float* __restrict__ flatness)
+__global__ __launch_bounds__(lpd_walk_threads<LDS>) void point_normals_kernel(const float* __restrict__ xyz, int ldx,
+                                                                              const int32_t* __restrict__ idx, int N, int K,
+                                                                              float* __restrict__ normals, float* __restrict__ flatness,
+                                                                              int vec4)
 {
-    extern __shared__ __attribute__((aligned(16))) float cloud[];      // [N][3] (LDS form)
-    constexpr int T = LDS ? PN_T_LDS : PN_T_L2;
-    const int tiles = (N + T - 1) / T;
-    const int b = blockIdx.x / tiles, i = (blockIdx.x % tiles) * T + (int)threadIdx.x;
-    const float* xc = xyz + (size_t)b * N * ldx;
-    if (LDS) {
-        for (int p = threadIdx.x; p < N; p += T) {
-            cloud[3 * p + 0] = xc[(size_t)p * ldx + 0];
-            cloud[3 * p + 1] = xc[(size_t)p * ldx + 1];
-            cloud[3 * p + 2] = xc[(size_t)p * ldx + 2];
-        }
-        __syncthreads();
-    }
-    if (i >= N) return;
-    float px, py, pz;
-    if (LDS) { px = cloud[3 * i]; py = cloud[3 * i + 1]; pz = cloud[3 * i + 2]; }
-    else { px = xc[(size_t)i * ldx]; py = xc[(size_t)i * ldx + 1]; pz = xc[(size_t)i * ldx + 2]; }
-    const int32_t* row = idx + ((size_t)b * N + i) * K;
-    const unsigned last = (unsigned)(N - 1);
+    LpdListWalk w;
+    if (!lpd_walk_open<LDS>(w, xyz, ldx, idx, N, K)) return;
     LpdFeatMoments m;
     lpd_feat_init(m);
-#pragma unroll 4
-    for (int j = 0; j < K; ++j) {
-        const unsigned n = min((unsigned)row[j], last);      // "any list is legal": an index outside the cloud reads its last point
-        float cx, cy, cz;
-        if (LDS) { cx = cloud[3 * n]; cy = cloud[3 * n + 1]; cz = cloud[3 * n + 2]; }
-        else { const float* pn = xc + (size_t)n * ldx; cx = pn[0]; cy = pn[1]; cz = pn[2]; }
-        lpd_feat_add(m, cx - px, cy - py, cz - pz);
-    }
+    lpd_walk<LDS, true>(w, K, vec4, [&](int, float dx, float dy, float dz) { lpd_feat_add(m, dx, dy, dz); });
     float n3[3], flat;
     lpd_icp_normal(m, K, n3, &flat);
-    const size_t mrow = (size_t)b * N + i;
+    const size_t mrow = w.mrow();
     normals[3 * mrow] = n3[0];
     normals[3 * mrow + 1] = n3[1];
     normals[3 * mrow + 2] = n3[2];
@@ -267,15 +242,10 @@ extern "C" int lpd_point_normals(const float* xyz, int ldx, const int32_t* idx, 
     LPD_CHECK_ARG((long long)B * N < (1ll << 31), "lpd_point_normals: B * N = %lld rows exceed 2^31", (long long)B * N);
     LPD_CHECK_ARG((const void*)normals != (const void*)xyz && (const void*)flatness != (const void*)xyz, "lpd_point_normals: an output aliases xyz");
     // A/B switch, read on every call (a test flips it inside one process): LPD_DEBUG=normals-l2 sends every cloud through the L2 form
-    const bool lds = N <= PN_LDS_MAX_N && !lpd_debug("normals-l2", 0);
-    const int T = lds ? PN_T_LDS : PN_T_L2;
-    const long long blocks = (long long)B * ((N + T - 1) / T);
-    LPD_CHECK_ARG(blocks < (1ll << 31), "lpd_point_normals: grid of %lld blocks", blocks);
-    if (lds)
-        hipLaunchKernelGGL(point_normals_kernel<true>, dim3((unsigned)blocks), dim3(T), (size_t)N * 3 * sizeof(float), stream, xyz, ldx, idx, N,
-                           K, normals, flatness);
-    else
-        hipLaunchKernelGGL(point_normals_kernel<false>, dim3((unsigned)blocks), dim3(T), 0, stream, xyz, ldx, idx, N, K, normals, flatness);
+    const LpdWalkPlan plan = lpd_walk_plan(idx, B, N, K, lpd_debug("normals-l2", 0) != 0);
+    LPD_CHECK_ARG(plan.blocks < (1ll << 31), "lpd_point_normals: grid of %lld blocks", plan.blocks);
+    hipLaunchKernelGGL(plan.lds ? point_normals_kernel<true> : point_normals_kernel<false>, dim3((unsigned)plan.blocks), dim3(plan.threads),
+                       plan.lds_bytes, stream, xyz, ldx, idx, N, K, normals, flatness, plan.vec4);
     LPD_CHECK_LAUNCH("lpd_point_normals");
     return LPD_OK;
 }

@@ -1545,8 +1545,8 @@ ALIGN_GRID, ALIGN_MAX_S, ALIGN_MAX_LAYERS, ALIGN_MAX_H, ALIGN_MAX_R = 128, 16, 4
 ALIGN_MAX_POINTS, ALIGN_MAX_PAIRS = 16384, 1 << 20
 
 
-def _align_arg(t, name, dtype, optional=False, what="align_pairs"):
-    """type and dtype of an argument of align_pairs, BEFORE its device: the host-side validation reads no device"""
+def _tensor_arg(what, t, name, dtype, optional=False):
+    """type and dtype of a tensor argument of `what`, BEFORE its device: the host-side validation reads no device"""
     if t is None and optional:
         return
     if not isinstance(t, torch.Tensor):
@@ -1555,14 +1555,48 @@ def _align_arg(t, name, dtype, optional=False, what="align_pairs"):
         raise TypeError(f"{what}: {name}: expected {dtype}, got {t.dtype}")
 
 
-def _align_table(t, name, what="align_pairs"):
+def _same_device(what, named):
+    """every (tensor or None, name) of `named` on the device, and on the device of the first"""
+    first, first_name = named[0]
+    for t, name in named:
+        _req(t, name, None if t is None else t.dtype)      # the device: no CPU path
+        if t is not None and t.device != first.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, {first_name} on {first.device}")
+
+
+def _cloud_table(what, t, name):
     """[T, N, 3] or [T, 1, N, 3] fp32 -> the [T, N, 3] view"""
-    _align_arg(t, name, torch.float32, what=what)
+    _tensor_arg(what, t, name, torch.float32)
     if t.dim() == 4 and t.shape[1] == 1:
         t = t[:, 0]
     if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or not 1 <= t.shape[1] <= ALIGN_MAX_POINTS:
         raise ValueError(f"{what}: {name} must be [T, N, 3] or [T, 1, N, 3] with T >= 1 and 1 <= N <= {ALIGN_MAX_POINTS}, got {tuple(t.shape)}")
     return t
+
+
+def _pair_tables(what, a, b, pairs, scale_a, scale_b, others=()):
+    """What the pair operations take in common: two cloud tables of one N, pairs [P, 2] int32 and the scale tables [TA] / [TB] or None
+    -> (a [TA, N, 3], b [TB, N, 3], TA, TB, N, P).  others: the (tensor, name, dtype, optional) of the operation's own tensor
+    arguments -- every type is checked before any shape"""
+    a, b = _cloud_table(what, a, "a"), _cloud_table(what, b, "b")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what}: a and b hold {a.shape[1]} and {b.shape[1]} points a cloud; one N")
+    TA, N, TB = a.shape[0], a.shape[1], b.shape[0]
+    _tensor_arg(what, pairs, "pairs", torch.int32)
+    _tensor_arg(what, scale_a, "scale_a", torch.float32, True)
+    _tensor_arg(what, scale_b, "scale_b", torch.float32, True)
+    for t, name, dtype, optional in others:
+        _tensor_arg(what, t, name, dtype, optional)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= ALIGN_MAX_PAIRS:      # = ICP_MAX_PAIRS
+        raise ValueError(f"{what}: pairs must be [P, 2] with 1 <= P <= 2^20, got {tuple(pairs.shape)}")
+    if scale_a is not None and tuple(scale_a.shape) != (TA,) or scale_b is not None and tuple(scale_b.shape) != (TB,):
+        raise ValueError(f"{what}: scale_a / scale_b must be [TA] = ({TA},) / [TB] = ({TB},)")
+    return a, b, TA, TB, N, pairs.shape[0]
+
+
+def _contiguous(*tensors):
+    """every tensor made contiguous, None kept: the caller holds the copies until its launch is enqueued and passes _ptr of each"""
+    return [None if t is None else t.contiguous() for t in tensors]
 
 
 def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a=None, scale_b=None, first=None, t0=None, want_yaw_scores=True):
@@ -1571,19 +1605,9 @@ def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a
     [R, 2] fp32 = the caller's (cos, sin) table, first [P] int32 or None, t0 [P, 2] fp32 metres or None, scale_a [TA] / scale_b [TB]
     fp32 metres per unit or None -- all on the device.  -> (best [P, 8] int32 = (h, dy, dx, score, nA, nB, 1, 0), yaw_scores [P, H]
     int32 or None).  Nothing is read back."""
-    a, b = _align_table(a, "a"), _align_table(b, "b")
-    if a.shape[1] != b.shape[1]:
-        raise ValueError(f"align_pairs: a and b hold {a.shape[1]} and {b.shape[1]} points a cloud; one N")
-    TA, N, TB = a.shape[0], a.shape[1], b.shape[0]
-    _align_arg(pairs, "pairs", torch.int32)
-    _align_arg(rot, "rot", torch.float32)
-    _align_arg(scale_a, "scale_a", torch.float32, True)
-    _align_arg(scale_b, "scale_b", torch.float32, True)
-    _align_arg(first, "first", torch.int32, True)
-    _align_arg(t0, "t0", torch.float32, True)
-    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= ALIGN_MAX_PAIRS:
-        raise ValueError(f"align_pairs: pairs must be [P, 2] with 1 <= P <= 2^20, got {tuple(pairs.shape)}")
-    P = pairs.shape[0]
+    what = "align_pairs"
+    a, b, TA, TB, N, P = _pair_tables(what, a, b, pairs, scale_a, scale_b, (
+        (rot, "rot", torch.float32, False), (first, "first", torch.int32, True), (t0, "t0", torch.float32, True)))
     if rot.dim() != 2 or rot.shape[1] != 2 or not 1 <= rot.shape[0] <= ALIGN_MAX_R:
         raise ValueError(f"align_pairs: rot must be [R, 2] with 1 <= R <= {ALIGN_MAX_R}, got {tuple(rot.shape)}")
     R = rot.shape[0]
@@ -1597,25 +1621,18 @@ def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a
     inv_cell, z0, inv_zcell = float(inv_cell), float(z0), float(inv_zcell)
     if not (0.0 < inv_cell < float("inf") and 0.0 < inv_zcell < float("inf") and abs(z0) < float("inf")):
         raise ValueError(f"align_pairs: inv_cell={inv_cell} inv_zcell={inv_zcell} (finite, > 0) z0={z0} (finite)")
-    if scale_a is not None and tuple(scale_a.shape) != (TA,) or scale_b is not None and tuple(scale_b.shape) != (TB,):
-        raise ValueError(f"align_pairs: scale_a / scale_b must be [TA] = ({TA},) / [TB] = ({TB},)")
     if first is not None and tuple(first.shape) != (P,):
         raise ValueError(f"align_pairs: first must be [P] = ({P},), got {tuple(first.shape)}")
     if t0 is not None and tuple(t0.shape) != (P, 2):
         raise ValueError(f"align_pairs: t0 must be [P, 2] = ({P}, 2), got {tuple(t0.shape)}")
-    for t, name in ((a, "a"), (b, "b"), (pairs, "pairs"), (rot, "rot"), (scale_a, "scale_a"), (scale_b, "scale_b"), (first, "first"), (t0, "t0")):
-        _req(t, name, None if t is None else t.dtype)      # the device: no CPU path
-        if t is not None and t.device != a.device:
-            raise ValueError(f"align_pairs: {name} is on {t.device}, a on {a.device}")
-    a, b = a.contiguous(), b.contiguous()
+    _same_device(what, ((a, "a"), (b, "b"), (pairs, "pairs"), (rot, "rot"), (scale_a, "scale_a"), (scale_b, "scale_b"), (first, "first"), (t0, "t0")))
     lib = _lib.load()
     best = torch.empty((P, 8), dtype=torch.int32, device=a.device)
     yaw_scores = torch.empty((P, H), dtype=torch.int32, device=a.device) if want_yaw_scores else None
     ws = torch.empty((max(int(lib.lpd_align_workspace_bytes(P, H)), 16),), dtype=torch.uint8, device=a.device)
-    _call("align_pairs", lib.lpd_align_pairs, _ptr(a), TA, _ptr(None if scale_a is None else scale_a.contiguous()), _ptr(b), TB,
-          _ptr(None if scale_b is None else scale_b.contiguous()), N, _ptr(pairs.contiguous()), P, _ptr(rot.contiguous()), R,
-          _ptr(None if first is None else first.contiguous()), H, _ptr(None if t0 is None else t0.contiguous()), inv_cell, S, z0, inv_zcell,
-          layers, _ptr(best), _ptr(yaw_scores), _ptr(ws), _stream())
+    a, b, pairs, rot, scale_a, scale_b, first, t0 = _contiguous(a, b, pairs, rot, scale_a, scale_b, first, t0)
+    _call("align_pairs", lib.lpd_align_pairs, _ptr(a), TA, _ptr(scale_a), _ptr(b), TB, _ptr(scale_b), N, _ptr(pairs), P, _ptr(rot), R,
+          _ptr(first), H, _ptr(t0), inv_cell, S, z0, inv_zcell, layers, _ptr(best), _ptr(yaw_scores), _ptr(ws), _stream())
     return best, yaw_scores
 
 
@@ -1625,24 +1642,13 @@ def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a
 ICP_MAX_POINTS, ICP_MAX_PAIRS, ICP_MAX_ITERS, ICP_MIN_INLIERS, ICP_MAX_DMAX, ICP_SUMS = 16384, 1 << 20, 64, 6, 16.0, 32      # csrc/lpd_icp_math.h
 
 
-def _icp_arg(what, t, name, dtype, optional=False):
-    _align_arg(t, name, dtype, optional, what)
-
-
-def _icp_devices(what, first, named):
-    for t, name in named:
-        _req(t, name, None if t is None else t.dtype)      # the device: no CPU path
-        if t is not None and t.device != first.device:
-            raise ValueError(f"{what}: {name} is on {t.device}, {named[0][1]} on {first.device}")
-
-
 def point_normals(xyz_rows, idx, B, N, want_flatness=False):
     """Unit normals of every point from its kNN list (lpd_point_normals; definition in include/lpd_hip.h).  xyz_rows [B*N, >= 3] fp32
     point-major, idx [B, N, K] int32 (knn_pm), 4 <= K <= 64, K <= N -> normals [B*N, 3] fp32, (0, 0, 0) where a neighbourhood has no
     extent or is not finite; with want_flatness also l3 / l2 [B*N] fp32.  Nothing is read back."""
     what = "point_normals"
-    _icp_arg(what, xyz_rows, "xyz_rows", torch.float32)
-    _icp_arg(what, idx, "idx", torch.int32)
+    _tensor_arg(what, xyz_rows, "xyz_rows", torch.float32)
+    _tensor_arg(what, idx, "idx", torch.int32)
     B, N = int(B), int(N)
     if B < 1 or N < 1 or B * N >= 1 << 31:
         raise ValueError(f"point_normals: B={B} N={N} (>= 1, B * N < 2^31)")
@@ -1653,7 +1659,7 @@ def point_normals(xyz_rows, idx, B, N, want_flatness=False):
     K = idx.shape[2]
     if not (4 <= K <= 64 and K <= N):
         raise ValueError(f"point_normals: need 4 <= K <= 64 and K <= N (K={K} N={N})")
-    _icp_devices(what, xyz_rows, ((xyz_rows, "xyz_rows"), (idx, "idx")))
+    _same_device(what, ((xyz_rows, "xyz_rows"), (idx, "idx")))
     idx = idx.contiguous()
     lib = _lib.load()
     normals = torch.empty((B * N, 3), dtype=torch.float32, device=xyz_rows.device)
@@ -1685,24 +1691,12 @@ def icp_pairs(a, b, normals_b, pairs, pose, dmax, min_inliers, scale_a=None, sca
     -> (pose [P, 12] float64, info [P, 4] int32 = (1 | -1, steps applied, steps refused, correspondences of the last pass),
     sums [iters + 1, P, 32] int64, nn [P, N] int32 or None).  Nothing is read back."""
     what = "icp_pairs"
-    a, b = _align_table(a, "a", what), _align_table(b, "b", what)
-    if a.shape[1] != b.shape[1]:
-        raise ValueError(f"icp_pairs: a and b hold {a.shape[1]} and {b.shape[1]} points a cloud; one N")
-    TA, N, TB = a.shape[0], a.shape[1], b.shape[0]
-    _icp_arg(what, normals_b, "normals_b", torch.float32)
-    _icp_arg(what, pairs, "pairs", torch.int32)
-    _icp_arg(what, pose, "pose", torch.float64)
-    _icp_arg(what, scale_a, "scale_a", torch.float32, True)
-    _icp_arg(what, scale_b, "scale_b", torch.float32, True)
+    a, b, TA, TB, N, P = _pair_tables(what, a, b, pairs, scale_a, scale_b, ((normals_b, "normals_b", torch.float32, False),
+                                                                           (pose, "pose", torch.float64, False)))
     if tuple(normals_b.shape) != (TB, N, 3):
         raise ValueError(f"icp_pairs: normals_b must be [TB, N, 3] = ({TB}, {N}, 3), got {tuple(normals_b.shape)}")
-    if pairs.dim() != 2 or pairs.shape[1] != 2 or not 1 <= pairs.shape[0] <= ICP_MAX_PAIRS:
-        raise ValueError(f"icp_pairs: pairs must be [P, 2] with 1 <= P <= 2^20, got {tuple(pairs.shape)}")
-    P = pairs.shape[0]
     if tuple(pose.shape) != (P, 12):
         raise ValueError(f"icp_pairs: pose must be [P, 12] = ({P}, 12), got {tuple(pose.shape)}")
-    if scale_a is not None and tuple(scale_a.shape) != (TA,) or scale_b is not None and tuple(scale_b.shape) != (TB,):
-        raise ValueError(f"icp_pairs: scale_a / scale_b must be [TA] = ({TA},) / [TB] = ({TB},)")
     try:
         iters = len(dmax) - 1
     except TypeError:
@@ -1713,9 +1707,7 @@ def icp_pairs(a, b, normals_b, pairs, pose, dmax, min_inliers, scale_a=None, sca
     if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or not ICP_MIN_INLIERS <= int(min_inliers) < 1 << 31:
         raise ValueError(f"icp_pairs: min_inliers={min_inliers!r} (an integer >= {ICP_MIN_INLIERS})")
     min_inliers = int(min_inliers)
-    _icp_devices(what, a, ((a, "a"), (b, "b"), (normals_b, "normals_b"), (pairs, "pairs"), (pose, "pose"), (scale_a, "scale_a"),
-                           (scale_b, "scale_b")))
-    a, b = a.contiguous(), b.contiguous()
+    _same_device(what, ((a, "a"), (b, "b"), (normals_b, "normals_b"), (pairs, "pairs"), (pose, "pose"), (scale_a, "scale_a"), (scale_b, "scale_b")))
     lib = _lib.load()
     dev = a.device
     pose = pose.contiguous().clone()
@@ -1723,9 +1715,9 @@ def icp_pairs(a, b, normals_b, pairs, pose, dmax, min_inliers, scale_a=None, sca
     sums = torch.empty((iters + 1, P, ICP_SUMS), dtype=torch.int64, device=dev)
     nn = torch.empty((P, N), dtype=torch.int32, device=dev) if want_nn else None
     ws = torch.empty((max(int(lib.lpd_icp_workspace_bytes(P, N, iters)), 16),), dtype=torch.uint8, device=dev)
-    _call("icp_pairs", lib.lpd_icp_pairs, _ptr(a), TA, _ptr(None if scale_a is None else scale_a.contiguous()), _ptr(b), TB,
-          _ptr(None if scale_b is None else scale_b.contiguous()), _ptr(normals_b.contiguous()), N, _ptr(pairs.contiguous()), P, dm, iters,
-          min_inliers, _ptr(pose), _ptr(info), _ptr(sums), _ptr(nn), _ptr(ws), _stream())
+    a, b, normals_b, pairs, scale_a, scale_b = _contiguous(a, b, normals_b, pairs, scale_a, scale_b)
+    _call("icp_pairs", lib.lpd_icp_pairs, _ptr(a), TA, _ptr(scale_a), _ptr(b), TB, _ptr(scale_b), _ptr(normals_b), N, _ptr(pairs), P, dm,
+          iters, min_inliers, _ptr(pose), _ptr(info), _ptr(sums), _ptr(nn), _ptr(ws), _stream())
     return pose, info, sums, nn
 
 

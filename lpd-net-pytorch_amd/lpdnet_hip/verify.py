@@ -34,7 +34,35 @@ def rot_table(R):
     return np.stack((np.cos(ang), np.sin(ang)), axis=1).astype(np.float32)
 
 
-class AlignSearch:
+class _Frozen:
+    """A validated search: the subclass's __slots__ are its fields, set once by its __init__ (_set), compared and hashed by value"""
+    __slots__ = ()
+
+    def _set(self, name, value):
+        object.__setattr__(self, name, value)
+
+    def _whole(self, v, name, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{type(self).__name__}: {name}={v!r} (an integer in {lo} .. {hi})")
+        return int(v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is frozen")
+
+    def __delattr__(self, name):
+        raise AttributeError(f"{type(self).__name__} is frozen")
+
+    def __repr__(self):
+        return type(self).__name__ + "(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and all(getattr(self, n) == getattr(other, n) for n in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, n) for n in self.__slots__))
+
+
+class AlignSearch(_Frozen):
     """The search of align_pairs, validated and frozen.  cell: metres per cell of the 128 x 128 grid (the coarse pass); shifts: S, the
     window is [-S, S]^2 cells; yaw_steps: H hypotheses 2 pi h / H; layers, z_lo, z_cell: the height layers [z_lo + l z_cell, z_lo +
     (l + 1) z_cell) in the cloud's centred metric frame; fine: a second pass with cell / 2, the 2 fine_div + 1 entries of the dense
@@ -42,11 +70,6 @@ class AlignSearch:
     __slots__ = ("cell", "shifts", "yaw_steps", "layers", "z_lo", "z_cell", "fine", "fine_div", "fine_shifts")
 
     def __init__(self, cell=0.5, shifts=8, yaw_steps=120, layers=4, z_lo=0.0, z_cell=2.0, fine=True, fine_div=8, fine_shifts=4):
-        def whole(v, name, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-                raise ValueError(f"AlignSearch: {name}={v!r} (an integer in {lo} .. {hi})")
-            return int(v)
-
         def real(v, name, positive):
             v = float(v)
             if not math.isfinite(v) or (positive and not v > 0.0):
@@ -54,35 +77,19 @@ class AlignSearch:
             return v
         if not isinstance(fine, (bool, np.bool_)):
             raise ValueError(f"AlignSearch: fine={fine!r} (a bool)")
-        set_ = object.__setattr__
-        set_(self, "cell", real(cell, "cell", True))
-        set_(self, "shifts", whole(shifts, "shifts", 0, ops.ALIGN_MAX_S))
-        set_(self, "yaw_steps", whole(yaw_steps, "yaw_steps", 1, ops.ALIGN_MAX_H))
-        set_(self, "layers", whole(layers, "layers", 1, ops.ALIGN_MAX_LAYERS))
-        set_(self, "z_lo", real(z_lo, "z_lo", False))
-        set_(self, "z_cell", real(z_cell, "z_cell", True))
-        set_(self, "fine", bool(fine))
-        set_(self, "fine_div", whole(fine_div, "fine_div", 1, (ops.ALIGN_MAX_H - 1) // 2))
-        set_(self, "fine_shifts", whole(fine_shifts, "fine_shifts", 0, ops.ALIGN_MAX_S))
+        self._set("cell", real(cell, "cell", True))
+        self._set("shifts", self._whole(shifts, "shifts", 0, ops.ALIGN_MAX_S))
+        self._set("yaw_steps", self._whole(yaw_steps, "yaw_steps", 1, ops.ALIGN_MAX_H))
+        self._set("layers", self._whole(layers, "layers", 1, ops.ALIGN_MAX_LAYERS))
+        self._set("z_lo", real(z_lo, "z_lo", False))
+        self._set("z_cell", real(z_cell, "z_cell", True))
+        self._set("fine", bool(fine))
+        self._set("fine_div", self._whole(fine_div, "fine_div", 1, (ops.ALIGN_MAX_H - 1) // 2))
+        self._set("fine_shifts", self._whole(fine_shifts, "fine_shifts", 0, ops.ALIGN_MAX_S))
         if self.fine and self.yaw_steps * self.fine_div > ops.ALIGN_MAX_R:
             raise ValueError(f"AlignSearch: yaw_steps * fine_div = {self.yaw_steps * self.fine_div} entries; at most {ops.ALIGN_MAX_R}")
         if self.fine and 2 * self.fine_div + 1 > self.yaw_steps * self.fine_div:
             raise ValueError(f"AlignSearch: the fine window of {2 * self.fine_div + 1} entries is longer than the dense table")
-
-    def __setattr__(self, name, value):
-        raise AttributeError("AlignSearch is frozen")
-
-    def __delattr__(self, name):
-        raise AttributeError("AlignSearch is frozen")
-
-    def __repr__(self):
-        return "AlignSearch(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
-
-    def __eq__(self, other):
-        return isinstance(other, AlignSearch) and all(getattr(self, n) == getattr(other, n) for n in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, n) for n in self.__slots__))
 
     @property
     def dense_steps(self):
@@ -108,7 +115,43 @@ class AlignSearch:
         return self._table(self.dense_steps, device)
 
 
-class Alignment:
+def _yaw_pose(yaw, translation):
+    """[.., 3, 4] float64 = (R | t): the rotation by yaw [..] about z and the translation [.., 2] in the plane"""
+    c, s = torch.cos(yaw), torch.sin(yaw)
+    M = torch.zeros(tuple(yaw.shape) + (3, 4), dtype=torch.float64, device=yaw.device)
+    M[..., 0, 0], M[..., 0, 1], M[..., 1, 0], M[..., 1, 1] = c, -s, s, c
+    M[..., 2, 2] = 1.0
+    M[..., 0, 3], M[..., 1, 3] = translation[..., 0], translation[..., 1]
+    return M
+
+
+class _PerPair:
+    """A result with one entry per pair: the subclass's __slots__ are tensors (or None) of leading shape [P]; center_a / center_b are
+    two of them"""
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for n in self.__slots__:
+            setattr(self, n, kw[n])
+
+    def _shaped(self, Q, K):
+        def v(t):
+            return None if t is None else t.reshape((Q, K) + tuple(t.shape[1:]))
+        return type(self)(**{n: v(getattr(self, n)) for n in self.__slots__})
+
+    def _with_centres(self, pose):
+        """[.., 4, 4] float64 of pose [.., 3, 4] = (R | t): p_B = R (p_A - c_A) + t + c_B"""
+        M = torch.zeros(tuple(pose.shape[:-2]) + (4, 4), dtype=torch.float64, device=pose.device)
+        M[..., :3, :] = pose
+        M[..., 3, 3] = 1.0
+        if self.center_a is not None:
+            M[..., :3, 3] -= (M[..., :3, :3] @ self.center_a[..., None])[..., 0]
+        if self.center_b is not None:
+            M[..., :3, 3] += self.center_b
+        return M
+
+
+class Alignment(_PerPair):
     """What align_pairs returns, one entry per pair (leading shape [P], or [Q, K] from verify_candidates): yaw float64 radians in
     [0, 2 pi) from the table index; translation [.., 2] float64 metres, so that p_B ~ R(yaw) p_A + translation in the clouds' centred
     metric frames; score, cells_a (at the winning yaw), cells_b int32; overlap = score / min(cells_a, cells_b), 0 where that is 0;
@@ -116,44 +159,47 @@ class Alignment:
     [.., 8] (or None) = the kernel's `best` of the two passes; center_a / center_b [.., 3] float64 or None."""
     __slots__ = ("yaw", "translation", "score", "cells_a", "cells_b", "overlap", "yaw_scores", "valid", "coarse", "fine", "center_a", "center_b")
 
-    def __init__(self, **kw):
-        for n in self.__slots__:
-            setattr(self, n, kw[n])
-
     def matrix(self):
         """[.., 4, 4] float64 taking A's metric frame into B's: a rotation about z and a translation.  With centres
         p_B = R (p_A - c_A) + t + c_B; the z translation comes from the centres only."""
-        c, s = torch.cos(self.yaw), torch.sin(self.yaw)
-        M = torch.zeros(tuple(self.yaw.shape) + (4, 4), dtype=torch.float64, device=self.yaw.device)
-        M[..., 0, 0], M[..., 0, 1], M[..., 1, 0], M[..., 1, 1] = c, -s, s, c
-        M[..., 2, 2] = 1.0
-        M[..., 3, 3] = 1.0
-        M[..., 0, 3], M[..., 1, 3] = self.translation[..., 0], self.translation[..., 1]
-        if self.center_a is not None:
-            M[..., :3, 3] -= (M[..., :3, :3] @ self.center_a[..., None])[..., 0]
-        if self.center_b is not None:
-            M[..., :3, 3] += self.center_b
-        return M
-
-    def _shaped(self, Q, K):
-        def v(t):
-            return None if t is None else t.reshape((Q, K) + tuple(t.shape[1:]))
-        return Alignment(**{n: v(getattr(self, n)) for n in self.__slots__})
+        return self._with_centres(_yaw_pose(self.yaw, self.translation))
 
 
-def _cloud_args(t, scale, center, name):
+def _cloud_args(what, t, scale, center, name):
     """-> (table, scale [T] fp32 or None, center [T, 3] or None) of a tensor or a Submaps"""
     from . import submap
     if isinstance(t, submap.Submaps):
         if scale is not None or center is not None:
-            raise ValueError(f"align_pairs: {name} is a Submaps: its scale and centre are taken from it")
+            raise ValueError(f"{what}: {name} is a Submaps: its scale and centre are taken from it")
         return t.x, t.scale, t.center
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"align_pairs: {name} must be a device tensor or a Submaps, got {type(t).__name__}")
+        raise TypeError(f"{what}: {name} must be a device tensor or a Submaps, got {type(t).__name__}")
     if center is not None:
         if not isinstance(center, torch.Tensor) or center.dim() != 2 or center.shape[1] != 3 or center.shape[0] != t.shape[0]:
-            raise ValueError(f"align_pairs: center_{name} must be a [T, 3] tensor")
+            raise ValueError(f"{what}: center_{name} must be a [T, 3] tensor")
     return t, scale, center
+
+
+def _pair_args(what, a, b, pairs, scale_a, scale_b, center_a, center_b):
+    """The clouds and pairs of align_pairs / refine_pairs -> (a, b, pairs [P, 2] int32, scale_a, scale_b, center_a, center_b): a, b
+    Submaps or tensors, pairs int32 or int64; no device is looked at"""
+    a, scale_a, center_a = _cloud_args(what, a, scale_a, center_a, "a")
+    b, scale_b, center_b = _cloud_args(what, b, scale_b, center_b, "b")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what}: pairs must be an int32 or int64 tensor")
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"{what}: pairs must be [P, 2], got {tuple(pairs.shape)}")
+    if pairs.dtype == torch.int64:      # a row number beyond int32 is outside every table: it becomes -1, "not read"
+        pairs = torch.where((pairs >= 0) & (pairs < (1 << 31) - 1), pairs, torch.full_like(pairs, -1)).to(torch.int32)
+    return a, b, pairs, scale_a, scale_b, center_a, center_b
+
+
+def _centres(c, rows, valid):
+    """[P, 3] float64 = the rows `rows` [P] of the centres c [T, 3], 0 where a pair is not valid; None without centres"""
+    if c is None:
+        return None
+    rows = rows.to(torch.int64).clamp(0, c.shape[0] - 1)
+    return torch.where(valid[:, None], c.to(device=valid.device, dtype=torch.float64)[rows], torch.zeros((), dtype=torch.float64, device=valid.device))
 
 
 def align_pairs(a, b, pairs, search=AlignSearch(), scale_a=None, scale_b=None, center_a=None, center_b=None):
@@ -163,17 +209,9 @@ def align_pairs(a, b, pairs, search=AlignSearch(), scale_a=None, scale_b=None, c
     torch on the device; nothing is read back."""
     if not isinstance(search, AlignSearch):
         raise TypeError(f"align_pairs: search must be an AlignSearch, got {type(search).__name__}")
-    a, scale_a, center_a = _cloud_args(a, scale_a, center_a, "a")
-    b, scale_b, center_b = _cloud_args(b, scale_b, center_b, "b")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype not in (torch.int32, torch.int64):
-        raise TypeError("align_pairs: pairs must be an int32 or int64 tensor")
-    if pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"align_pairs: pairs must be [P, 2], got {tuple(pairs.shape)}")
+    a, b, pairs, scale_a, scale_b, center_a, center_b = _pair_args("align_pairs", a, b, pairs, scale_a, scale_b, center_a, center_b)
     ops._req(a, "a")
     dev = a.device
-    TA, TB = a.shape[0], b.shape[0]
-    if pairs.dtype == torch.int64:      # a row number beyond int32 is outside every table: it becomes -1, "not read"
-        pairs = torch.where((pairs >= 0) & (pairs < (1 << 31) - 1), pairs, torch.full_like(pairs, -1)).to(torch.int32)
     s = search
     H = s.yaw_steps
     coarse, yaw_scores = ops.align_pairs(a, b, pairs, s.coarse_table(dev), H, 1.0 / s.cell, s.shifts, s.z_lo, 1.0 / s.z_cell, s.layers,
@@ -200,17 +238,12 @@ def align_pairs(a, b, pairs, search=AlignSearch(), scale_a=None, scale_b=None, c
     score, cells_a, cells_b = last[:, 3], last[:, 4], last[:, 5]
     least = torch.minimum(cells_a, cells_b)
     overlap = torch.where(least > 0, score.to(torch.float64) / least.clamp(min=1).to(torch.float64), zero)
-
-    def centre(c, col, T):
-        if c is None:
-            return None
-        rows = pairs[:, col].to(torch.int64).clamp(0, T - 1)
-        return torch.where(valid[:, None], c.to(device=dev, dtype=torch.float64)[rows], zero)
     return Alignment(yaw=yaw, translation=translation, score=score, cells_a=cells_a, cells_b=cells_b, overlap=overlap, yaw_scores=yaw_scores,
-                     valid=valid, coarse=coarse, fine=fine, center_a=centre(center_a, 0, TA), center_b=centre(center_b, 1, TB))
+                     valid=valid, coarse=coarse, fine=fine, center_a=_centres(center_a, pairs[:, 0], valid),
+                     center_b=_centres(center_b, pairs[:, 1], valid))
 
 
-class RefineSearch:
+class RefineSearch(_Frozen):
     """The search of refine_pairs, validated and frozen.  k: neighbours a normal of b is made from (4 .. 64); dmax: the trimming
     distance in metres, one number or a sequence of `iterations` numbers, one a pass; iterations: steps (0 .. 64); min_inliers: a
     step with fewer correspondences is refused (>= 6); final_dmax: the distance of the pass behind the last step, which makes
@@ -218,11 +251,6 @@ class RefineSearch:
     __slots__ = ("k", "dmax", "iterations", "min_inliers", "final_dmax")
 
     def __init__(self, k=16, dmax=1.0, iterations=8, min_inliers=32, final_dmax=None):
-        def whole(v, name, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-                raise ValueError(f"RefineSearch: {name}={v!r} (an integer in {lo} .. {hi})")
-            return int(v)
-
         def dist(v, name):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
                 raise ValueError(f"RefineSearch: {name}={v!r} (a number)")
@@ -230,10 +258,9 @@ class RefineSearch:
             if not (0.0 < v <= ops.ICP_MAX_DMAX and 0.0 < float(np.float32(v)) <= ops.ICP_MAX_DMAX):      # false for NaN
                 raise ValueError(f"RefineSearch: {name}={v!r} (finite, > 0, <= {ops.ICP_MAX_DMAX})")
             return v
-        set_ = object.__setattr__
-        set_(self, "k", whole(k, "k", 4, 64))
-        set_(self, "iterations", whole(iterations, "iterations", 0, ops.ICP_MAX_ITERS))
-        set_(self, "min_inliers", whole(min_inliers, "min_inliers", ops.ICP_MIN_INLIERS, (1 << 31) - 1))
+        self._set("k", self._whole(k, "k", 4, 64))
+        self._set("iterations", self._whole(iterations, "iterations", 0, ops.ICP_MAX_ITERS))
+        self._set("min_inliers", self._whole(min_inliers, "min_inliers", ops.ICP_MIN_INLIERS, (1 << 31) - 1))
         if isinstance(dmax, (list, tuple, np.ndarray)):
             if len(dmax) != self.iterations:
                 raise ValueError(f"RefineSearch: dmax holds {len(dmax)} entries; iterations = {self.iterations}")
@@ -247,23 +274,8 @@ class RefineSearch:
                 final_dmax = dmax
             else:
                 final_dmax = sched[-1]
-        set_(self, "dmax", sched)
-        set_(self, "final_dmax", dist(final_dmax, "final_dmax"))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("RefineSearch is frozen")
-
-    def __delattr__(self, name):
-        raise AttributeError("RefineSearch is frozen")
-
-    def __repr__(self):
-        return "RefineSearch(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
-
-    def __eq__(self, other):
-        return isinstance(other, RefineSearch) and all(getattr(self, n) == getattr(other, n) for n in self.__slots__)
-
-    def __hash__(self):
-        return hash(tuple(getattr(self, n) for n in self.__slots__))
+        self._set("dmax", sched)
+        self._set("final_dmax", dist(final_dmax, "final_dmax"))
 
     @property
     def schedule(self):
@@ -271,7 +283,7 @@ class RefineSearch:
         return self.dmax + (self.final_dmax,)
 
 
-class Refinement:
+class Refinement(_PerPair):
     """What refine_pairs returns, one entry per pair (leading shape [P], or [Q, K] from refine_candidates): pose [.., 3, 4] float64 =
     (R | t), p_B ~ R p_A + t in the clouds' centred metric frames; valid bool (False: the pair names a row outside its table, or its
     alignment was not valid; its pose is the start); steps, refused int32 = the steps applied and refused; inliers int32 = the
@@ -280,25 +292,9 @@ class Refinement:
     float64 or None."""
     __slots__ = ("pose", "valid", "steps", "refused", "inliers", "inlier_share", "rms", "sums", "nn", "center_a", "center_b")
 
-    def __init__(self, **kw):
-        for n in self.__slots__:
-            setattr(self, n, kw[n])
-
     def matrix(self):
         """[.., 4, 4] float64 taking A's metric frame into B's.  With centres p_B = R (p_A - c_A) + t + c_B, as Alignment.matrix()."""
-        M = torch.zeros(tuple(self.pose.shape[:-2]) + (4, 4), dtype=torch.float64, device=self.pose.device)
-        M[..., :3, :] = self.pose
-        M[..., 3, 3] = 1.0
-        if self.center_a is not None:
-            M[..., :3, 3] -= (M[..., :3, :3] @ self.center_a[..., None])[..., 0]
-        if self.center_b is not None:
-            M[..., :3, 3] += self.center_b
-        return M
-
-    def _shaped(self, Q, K):
-        def v(t):
-            return None if t is None else t.reshape((Q, K) + tuple(t.shape[1:]))
-        return Refinement(**{n: v(getattr(self, n)) for n in self.__slots__})
+        return self._with_centres(self.pose)
 
 
 def point_normals(b, k=16):
@@ -306,7 +302,7 @@ def point_normals(b, k=16):
     neighbours (ops.knn_pm, then ops.point_normals); (0, 0, 0) where a neighbourhood has no extent or is not finite."""
     from . import submap
     x = b.x if isinstance(b, submap.Submaps) else b
-    x = ops._align_table(x, "b", "point_normals")
+    x = ops._cloud_table("point_normals", x, "b")
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 4 <= int(k) <= 64 or int(k) > x.shape[1]:
         raise ValueError(f"point_normals: k={k!r} (an integer in 4 .. 64, at most N = {x.shape[1]})")
     ops._req(x, "b")
@@ -335,12 +331,7 @@ def _init_pose(init, P, dev):
     if init is None:
         return torch.eye(3, 4, dtype=torch.float64, device=dev).reshape(1, 12).repeat(P, 1), None
     if isinstance(init, Alignment):
-        c, s = torch.cos(init.yaw), torch.sin(init.yaw)
-        M = torch.zeros((P, 3, 4), dtype=torch.float64, device=dev)
-        M[:, 0, 0], M[:, 0, 1], M[:, 1, 0], M[:, 1, 1] = c, -s, s, c
-        M[:, 2, 2] = 1.0
-        M[:, 0, 3], M[:, 1, 3] = init.translation[:, 0], init.translation[:, 1]
-        return M.reshape(P, 12), init.valid
+        return _yaw_pose(init.yaw, init.translation).reshape(P, 12), init.valid
     ops._req(init, "init", torch.float64)
     if init.dim() == 3 and init.shape[1] == 4:
         init = init[:, :3, :]
@@ -356,19 +347,12 @@ def refine_pairs(a, b, pairs, init=None, search=RefineSearch(), normals_b=None, 
     here otherwise.  -> Refinement.  Nothing is read back."""
     if not isinstance(search, RefineSearch):
         raise TypeError(f"refine_pairs: search must be a RefineSearch, got {type(search).__name__}")
-    a, scale_a, center_a = _cloud_args(a, scale_a, center_a, "a")
-    b, scale_b, center_b = _cloud_args(b, scale_b, center_b, "b")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype not in (torch.int32, torch.int64):
-        raise TypeError("refine_pairs: pairs must be an int32 or int64 tensor")
-    if pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"refine_pairs: pairs must be [P, 2], got {tuple(pairs.shape)}")
-    a3, b3 = ops._align_table(a, "a", "refine_pairs"), ops._align_table(b, "b", "refine_pairs")
-    TA, TB, N, P = a3.shape[0], b3.shape[0], a3.shape[1], pairs.shape[0]
+    a, b, pairs, scale_a, scale_b, center_a, center_b = _pair_args("refine_pairs", a, b, pairs, scale_a, scale_b, center_a, center_b)
+    a3, b3 = ops._cloud_table("refine_pairs", a, "a"), ops._cloud_table("refine_pairs", b, "b")
+    TB, N, P = b3.shape[0], a3.shape[1], pairs.shape[0]
     _check_init(init, P)
     ops._req(a3, "a")
     dev = a3.device
-    if pairs.dtype == torch.int64:      # a row number beyond int32 is outside every table: it becomes -1, "not read"
-        pairs = torch.where((pairs >= 0) & (pairs < (1 << 31) - 1), pairs, torch.full_like(pairs, -1)).to(torch.int32)
     pose0, ok = _init_pose(init, P, dev)
     if ok is not None:
         pairs = torch.where(ok[:, None], pairs, torch.full_like(pairs, -1))
@@ -381,15 +365,9 @@ def refine_pairs(a, b, pairs, init=None, search=RefineSearch(), normals_b=None, 
     m = last[:, 0]
     zero = torch.zeros((), dtype=torch.float64, device=dev)
     rms = torch.where(m > 0, torch.sqrt(last[:, 28].to(torch.float64) / m.clamp(min=1).to(torch.float64)) / 1024.0, zero)
-
-    def centre(c, col, T):
-        if c is None:
-            return None
-        rows = pairs[:, col].to(torch.int64).clamp(0, T - 1)
-        return torch.where(valid[:, None], c.to(device=dev, dtype=torch.float64)[rows], zero)
     return Refinement(pose=pose.reshape(P, 3, 4), valid=valid, steps=info[:, 1], refused=info[:, 2], inliers=info[:, 3],
                       inlier_share=info[:, 3].to(torch.float64) / float(N), rms=rms, sums=sums.permute(1, 0, 2), nn=nn,
-                      center_a=centre(center_a, 0, TA), center_b=centre(center_b, 1, TB))
+                      center_a=_centres(center_a, pairs[:, 0], valid), center_b=_centres(center_b, pairs[:, 1], valid))
 
 
 class Verification:

@@ -110,6 +110,29 @@ def test_one_table_for_both_clouds(cuda, small):
     assert got[0][0].tolist()[:4] == [0, 0, 0, int(want[0][0, 4])] and want[0][0, 4] == want[0][0, 5]      # a cloud against itself
 
 
+def _strided(t, fill):
+    """the values of t as the leading columns of a tensor one column wider: not contiguous"""
+    wide = torch.full(tuple(t.shape[:-1]) + (t.shape[-1] + 1,), fill, dtype=t.dtype, device=t.device)
+    wide[..., :-1] = t
+    v = wide[..., :-1]
+    assert not v.is_contiguous()
+    return v
+
+
+def test_non_contiguous_arguments_equal_the_contiguous_ones(cuda, small):
+    """two distinct tables of one size, pairs and the rotation table as strided views: the wrapper's contiguous copies all live
+    until the launch, so none of them takes another's memory"""
+    A, B, rot = small
+    a, b = torch.from_numpy(A).to(cuda), torch.from_numpy(B).to(cuda)
+    pairs = torch.tensor([[0, 0], [1, 2], [2, 1], [0, 1]], dtype=torch.int32, device=cuda)
+    r = torch.from_numpy(rot).to(cuda)
+    want = ops.align_pairs(a, b, pairs, r, 16, 2.0, 4, 0.0, 0.5, 4)
+    got = ops.align_pairs(_strided(a, float("nan")), _strided(b, float("nan")), _strided(pairs, -1), _strided(r, float("nan")), 16, 2.0, 4, 0.0, 0.5, 4)
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(want[0], ops.align_pairs(b, b, pairs, r, 16, 2.0, 4, 0.0, 0.5, 4)[0])      # b in a's place gives another answer
+
+
 def test_scale_tables(cuda, small):
     A, B, rot = small
     sa, sb = np.array([25.0, 31.5, 0.9], dtype=np.float32), np.array([27.25, 1.0, 40.0], dtype=np.float32)

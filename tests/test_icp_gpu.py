@@ -11,6 +11,7 @@ import torch
 
 import align_ref as AR
 import icp_ref as R
+import walk_forms
 from lpdnet_hip import _lib, ops, verify
 from test_icp_cpu import NORMAL_GATE, NORMAL_MIN_GAP, QUALITY_GATE_DEG, QUALITY_GATE_M, _corner, _patches, _small_pose
 
@@ -107,6 +108,23 @@ def test_one_table_for_both_clouds_and_scale_tables(cuda):
     want = _ref(An, Bn, nB, pairs, pose, [1.0], scaleA=sa, scaleB=sb)
     assert _equal(got, want) and want[2][0, :, 0].min() > 300
     assert not np.array_equal(want[2], _ref(An, Bn, nB, pairs, pose, [1.0])[2])      # the scales matter
+
+
+def test_non_contiguous_arguments_equal_the_contiguous_ones(cuda):
+    """a, b and normals_b of one size (TA = TB), pairs and pose as strided views: the wrapper's contiguous copies all live until the
+    launch, so none of them takes another's memory"""
+    from test_align_gpu import _strided
+    g = np.random.default_rng(14)
+    A, B = _tables(1000, TA=3, TB=3, seed=3)
+    a, b, nb = _up(cuda, A, f32), _up(cuda, B, f32), _up(cuda, _device_normals(cuda, B), f32)
+    pairs = torch.tensor([[0, 0], [1, 2], [2, 1], [0, 1]], dtype=torch.int32, device=cuda)
+    pose = _up(cuda, np.stack([_small_pose(g, 0.03, 0.3) for _ in range(4)]), np.float64)
+    nan = float("nan")
+    want = ops.icp_pairs(a, b, nb, pairs, pose, [1.0, 1.0], 6, want_nn=True)
+    got = ops.icp_pairs(_strided(a, nan), _strided(b, nan), _strided(nb, nan), _strided(pairs, -1), _strided(pose, nan), [1.0, 1.0], 6, want_nn=True)
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(got, want)) and int(want[2][0, :, 0].min()) > 250      # the clouds do overlap
+    assert not torch.equal(want[2], ops.icp_pairs(b, b, nb, pairs, pose, [1.0, 1.0], 6)[2])      # b in a's place gives other sums
 
 
 # ---- 2. ties and edges -------------------------------------------------------------------------------------------------------------
@@ -336,6 +354,44 @@ def test_point_normals_k_equal_to_n(cuda, N):
             assert (1.0 - np.abs((n[b].astype(np.float64) * ref).sum(axis=1)))[sel].max() <= NORMAL_GATE
         assert np.abs(np.linalg.norm(n[b].astype(np.float64), axis=1) - 1.0).max() < 2e-7
     assert used >= N
+
+
+# (B, N, K): the cases of tests/test_local_features_gpu.py WALK_CASES -- one launch that stages cloud 0 in 16-byte pieces and cloud 1
+# (804 bytes in) by the float, K on both sides of the int4 list read, a second tile with one live lane in either form
+WALK_CASES = [(2, 67, 4), (2, 67, 5), (2, 67, 7), (2, 67, 8), (1, 513, 8), (1, 257, 8)]
+
+
+@pytest.mark.parametrize("B,N,K", WALK_CASES)
+def test_point_normals_every_read_path_gives_the_same_bits(cuda, monkeypatch, B, N, K):
+    """The plain input is held to fp64 eigh (the gate of test_point_normals_k_equal_to_n); every other layout of the same input
+    (walk_forms), and all of them again in the L2 form, give its bits in the normals and the flatness."""
+    g = np.random.default_rng(1000 * N + K)
+    x = np.stack([np.column_stack((g.uniform(-2, 2, (N, 2)), g.normal(0, 0.01, N))) @ R.rot_xyz(0.3, -0.2, 0.5).T for _ in range(B)]).astype(f32)
+    idx = np.stack([R.knn_lists(c, K) for c in x])
+    rows, idx_t = _up(cuda, x, f32).view(B * N, 3), _up(cuda, idx, np.int32)
+
+    def run(r, i):
+        n, flat = ops.point_normals(r, i, B, N, want_flatness=True)
+        torch.cuda.synchronize()
+        return n.cpu().numpy(), flat.cpu().numpy()
+    base, fbase = run(rows, idx_t)
+    used = 0
+    for b in range(B):
+        nb = base.reshape(B, N, 3)[b].astype(np.float64)
+        ref, gap = R.eigh_normals(x[b], idx[b])
+        sel = gap >= NORMAL_MIN_GAP      # a few neighbours can be nearly collinear: such a point has no normal to compare
+        used += int(sel.sum())
+        assert (1.0 - np.abs((nb * ref).sum(axis=1)))[sel].max() <= NORMAL_GATE
+        assert np.abs(np.linalg.norm(nb, axis=1) - 1.0).max() < 2e-7
+    assert 2 * used > B * N
+    variants = walk_forms.forms(rows, idx_t)
+    for l2 in (False, True):
+        if l2:
+            monkeypatch.setenv("LPD_DEBUG", "normals-l2")
+        for name, r, i in variants + ([("plain", rows, idx_t)] if l2 else []):
+            got, fgot = run(r, i)
+            assert np.array_equal(got.view(np.int32), base.view(np.int32)) and np.array_equal(fgot.view(np.int32), fbase.view(np.int32)), \
+                (name, "L2" if l2 else "LDS")
 
 
 # ---- 6. the wrapper ----------------------------------------------------------------------------------------------------------------

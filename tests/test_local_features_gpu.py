@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import local_features_ref as R
+import walk_forms
 from oracle import lpd_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,39 @@ def test_both_forms_agree_on_a_second_cloud_kind(cuda, monkeypatch):
     _l2_form(monkeypatch)
     l2, _, k_l2 = _run(cuda, x, idx=idx, candidates=CANDIDATES, want_k=True)
     assert np.array_equal(lds.view(np.int32), l2.view(np.int32)) and np.array_equal(k_lds, k_l2)
+
+
+# (B, N, K, candidates).  B = 2, N = 67 with ldx = 3: the second cloud starts 804 bytes in, so one launch stages cloud 0 in 16-byte
+# pieces and cloud 1 by the float; 3 N is no multiple of 4 (the scalar tail) and the last tile is mostly idle lanes.  K = 7: 4-byte
+# list loads and a last group of three; K = 8 and 12: int4 pieces.  N = 513 (LDS form) and N = 257 (L2 form): a second tile with one
+# live lane.
+WALK_CASES = [(2, 67, 7, None), (2, 67, 8, None), (2, 67, 12, (4, 8, 12)), (1, 513, 8, None), (1, 257, 8, None)]
+
+
+@pytest.mark.parametrize("B,N,K,cand", WALK_CASES)
+def test_every_read_path_gives_the_same_bits(cuda, monkeypatch, B, N, K, cand):
+    """The plain input is held to the fp64 reference; every other layout of the same input (walk_forms), and all of them again in
+    the L2 form, give its bits in all ten columns and kopt."""
+    from lpdnet_hip import ops
+    x = _clouds(B, N, 9, ("slab", "cube"))
+    idx = R.knn_lists(x, K)
+    rows, idx_t = torch.from_numpy(x).to(cuda).view(B * N, 3), torch.from_numpy(idx).to(cuda)
+
+    def run(r, i):
+        out, kopt = ops.local_features(r, i, B, N, candidates=cand, want_k=True)
+        torch.cuda.synchronize()
+        return out.cpu().numpy(), kopt.cpu().numpy()
+    base, kbase = run(rows, idx_t)
+    assert np.isin(kbase, cand if cand else (K,)).all()
+    ref, gap = R.features(x, idx, kopt=kbase.reshape(B, N))
+    assert not R.check_columns(base.reshape(B, N, 10), ref, gap, f"walk/B{B}/N{N}/K{K}" + ("/adaptive" if cand else ""))
+    variants = walk_forms.forms(rows, idx_t)
+    for l2 in (False, True):
+        if l2:
+            _l2_form(monkeypatch)
+        for name, r, i in variants + ([("plain", rows, idx_t)] if l2 else []):
+            got, kgot = run(r, i)
+            assert np.array_equal(got.view(np.int32), base.view(np.int32)) and np.array_equal(kgot, kbase), (name, "L2" if l2 else "LDS")
 
 
 # ---- 4. translated clouds: the moments must be centred on the query point -------------------------------------------------------
