@@ -736,6 +736,49 @@ int lpd_icp_pairs(const float* A, int TA, const float* scaleA, const float* B, i
                   const int32_t* pairs, int P, const float* dmax, int iters, int min_inliers, double* pose, int32_t* info,
                   long long* sums, int32_t* nn, void* ws, void* stream);
 
+/*
+ * Sequence-consistent place retrieval (csrc/lpd_seqmatch.hip; arithmetic in csrc/lpd_seq_math.h): every retrieved candidate of a
+ * query is scored along the drive -- a short sequence of consecutive query rows against a line of consecutive database rows, at a
+ * few velocities and shifts (Milford and Wyeth, "SeqSLAM", ICRA 2012; on these descriptors Liu et al., "SeqLPD", IROS 2019) -- and
+ * the candidates are re-ranked by that score.  The step between lpd_retrieval_topk / lpd_recall_pairs' topk_idx and lpd_align_pairs.
+ * This comment is the specification, and lpd_seq_math.h settles every detail it leaves open.  Integers only behind the quantisation.
+ *   Q [nq][ldq], D [nd][ldd]  fp32 descriptor tables in drive order; dim 64, 128 or 256; ldq, ldd multiples of 4, tables 16-byte
+ *            aligned (as for lpd_recall_pairs); Q and D may be the same memory.  NaN and inf allowed.
+ *   q_off [SQ+1], d_off [SD+1]  int32 run offsets rising from 0 to nq / nd.  The run of a row x is found by a lower-bound search; a
+ *            sequence never crosses a run boundary.  Only compared, never used as an address.
+ *   cand     [nq][K] int32 database rows, 1 <= K <= 64.  An entry < 0 or >= nd is SKIPPED: none of its rows are read.
+ *   steps    [V][L] int32, L = 2h + 1, 1 <= h <= 15, the CALLER's table (made once on the host from the velocities): steps[v][t+h] is
+ *            the database offset of term t, steps[v][h] == 0.  The device never sees a velocity as a float.
+ *   S        shifts s = -S .. S of the candidate row, 0 <= S <= 15; the caller keeps max|steps| + S <= 15.  V (2S+1) <= 1024.
+ *   min_terms  1 .. L.
+ * Distance of query row a and database row b, the arithmetic of lpd_retrieval_topk: squared norms by an fmaf chain in channel order,
+ * q.d on the exact f32-input MFMA (the k-ordered fmaf chain), x = (qn + dn) - (2.0f * dot).  A NaN x makes the term "not counted";
+ * otherwise d2 = fmaxf(x, 0.0f) and dq = (int) rintf(fminf(d2, 16.0f) * 16384.0f): the quantum is 2^-14, dq <= 2^18.
+ * Candidate (i, r) has the centre row j = cand[i][r].  Hypothesis e = v (2S+1) + (s + S).  Term t = -h .. h pairs query row a = i + t
+ * with database row b = j + s + steps[v][t+h]; it is counted iff a lies in the run of i, b lies in the run of j + s, and x is not NaN
+ * (and b lies in j-15 .. j+15, which the caller's table guarantees).  sum_e = the sum of the counted dq (< 2^23), n_e their number.
+ * The hypothesis is valid iff 0 <= j+s < nd, j+s lies in the run of j, and n_e >= min_terms.  e1 is better than e2 iff
+ * (int64) sum1 * n2 < (int64) sum2 * n1; equal means go to the lower e: a total order, any reduction order gives the same winner.
+ *   best     [nq][K][4] int32 = (e, sum, n, j + s) of the best valid hypothesis; (-1, 0, 0, -1) for a skipped candidate or one
+ *            without a valid hypothesis.
+ *   order    [nq][K] int32: a permutation of 0 .. K-1 per query; valid candidates first by the same comparison of means (ties to
+ *            the lower r), then the others in retrieval order.
+ *   block    [nq][K][32][32] int32, or NULL: entry [t+h][b'] = dq of query row i + t, t = -h .. h, against database row j - 15 + b',
+ *            whatever runs the rows lie in; -1 where either row is outside its table or x is NaN, in the rows t + h > 2h, in row 31
+ *            and column 31, and everywhere for a skipped candidate.
+ *   ws       nq + nd floats, the caller's: the squared norms.  No state between calls.
+ * No atomics of any kind: the same bits in every launch.  Nothing outside the tables is read whatever cand, steps and the offsets
+ * hold.  The call only enqueues.
+ */
+#define LPD_SEQ_BAND 15
+#define LPD_SEQ_QBITS 14
+#define LPD_SEQ_KMAX 64
+#define LPD_SEQ_MAX_HYP 1024
+int lpd_seq_match(const float* Q, int ldq, int nq, const int32_t* q_off, int SQ,
+                  const float* D, int ldd, int nd, const int32_t* d_off, int SD, int dim,
+                  const int32_t* cand, int K, const int32_t* steps, int V, int h, int S, int min_terms,
+                  int32_t* best, int32_t* order, int32_t* block, float* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -2779,6 +2779,86 @@ def hard_negatives(table, Q, cand, k):
     return pos, dist
 
 
+# ------------------------------------------------------------------------------------------------
+# sequence scoring of retrieved candidates along the drive (csrc/lpd_seqmatch.hip)
+# ------------------------------------------------------------------------------------------------
+SEQ_BAND, SEQ_QBITS, SEQ_KMAX, SEQ_MAX_HYP = (_lib.DEFINES["LPD_SEQ_" + n] for n in ("BAND", "QBITS", "KMAX", "MAX_HYP"))
+
+
+def _seq_offsets(off, name, rows):
+    """run offsets of seq_match, validated on the host as recall_pairs validates its own: int32, rising from 0 to exactly the table's
+    rows; None is one run -> host numpy int32"""
+    import numpy as np
+    if off is None:
+        return np.array([0, rows], dtype=np.int32)
+    off = _index_array(off, name, 1)
+    if off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != rows:
+        raise ValueError(f"seq_match: {name} must rise from 0 to the {rows} table rows")
+    return off
+
+
+def seq_steps(steps, S):
+    """the steps table of seq_match checked on the host -> (numpy int32 [V, L] contiguous, h): L = 2h + 1 odd, 1 <= h <= SEQ_BAND, the
+    middle column 0, max|steps| + S <= SEQ_BAND, V (2S + 1) <= SEQ_MAX_HYP"""
+    import numpy as np
+    steps = _index_array(steps, "steps", 2)
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 0 <= int(S) <= SEQ_BAND:
+        raise ValueError(f"seq_match: S={S!r} (an integer in 0 .. {SEQ_BAND})")
+    S = int(S)
+    V, L = steps.shape
+    if V < 1 or L % 2 != 1 or not 1 <= (L - 1) // 2 <= SEQ_BAND:
+        raise ValueError(f"seq_match: steps must be [V >= 1, L = 2h + 1] with 1 <= h <= {SEQ_BAND}, got {steps.shape}")
+    h = (L - 1) // 2
+    if (steps[:, h] != 0).any():
+        raise ValueError("seq_match: steps[v][h] must be 0 (term 0 is the candidate's own row)")
+    if int(np.abs(steps.astype(np.int64)).max()) + S > SEQ_BAND:
+        raise ValueError(f"seq_match: max|steps| + S = {int(np.abs(steps.astype(np.int64)).max())} + {S} exceeds the band of {SEQ_BAND} rows")
+    if V * (2 * S + 1) > SEQ_MAX_HYP:
+        raise ValueError(f"seq_match: V (2S + 1) = {V * (2 * S + 1)} hypotheses; at most {SEQ_MAX_HYP}")
+    return np.ascontiguousarray(steps, dtype=np.int32), h
+
+
+def seq_match(Q, D, cand, steps, S, min_terms, q_off=None, d_off=None, want_block=False):
+    """Score every retrieved candidate along the drive (lpd_seq_match; definition in include/lpd_hip.h).  Q [nq, dim], D [nd, dim] fp32
+    on the device in drive order (rows with a leading dimension allowed; may be one tensor), cand [nq, K] int32 on the device (entries
+    < 0 or >= nd are skipped), steps [V, 2h + 1] int32 and q_off / d_off (None: one run) on the HOST (numpy or tensor; checked there).
+    -> (best [nq, K, 4] int32 = (e, sum, n, row), order [nq, K] int32, block [nq, K, 32, 32] int32 or None).  Nothing is read back."""
+    import numpy as np
+    what = "seq_match"
+    _tensor_arg(what, Q, "Q", torch.float32)
+    _tensor_arg(what, D, "D", torch.float32)
+    _tensor_arg(what, cand, "cand", torch.int32)
+    if Q.dim() != 2 or D.dim() != 2 or Q.shape[1] != D.shape[1] or Q.shape[0] < 1 or D.shape[0] < 1:
+        raise ValueError(f"seq_match: Q and D must be [nq >= 1, dim] and [nd >= 1, dim] of one dim, got {tuple(Q.shape)} and {tuple(D.shape)}")
+    if Q.shape[1] > 256:
+        raise ValueError(f"seq_match: descriptors of {Q.shape[1]} channels (at most 256)")
+    nq, nd = Q.shape[0], D.shape[0]
+    if cand.dim() != 2 or cand.shape[0] != nq or not 1 <= cand.shape[1] <= SEQ_KMAX:
+        raise ValueError(f"seq_match: cand must be [nq, K] = [{nq}, 1 .. {SEQ_KMAX}], got {tuple(cand.shape)}")
+    K = cand.shape[1]
+    steps, h = seq_steps(steps, S)
+    S, V, L = int(S), steps.shape[0], steps.shape[1]
+    if isinstance(min_terms, bool) or not isinstance(min_terms, (int, np.integer)) or not 1 <= int(min_terms) <= L:
+        raise ValueError(f"seq_match: min_terms={min_terms!r} (an integer in 1 .. {L})")
+    qo, do = _seq_offsets(q_off, "q_off", nq), _seq_offsets(d_off, "d_off", nd)
+    _same_device(what, ((Q, "Q"), (D, "D"), (cand, "cand")))
+    same = Q.data_ptr() == D.data_ptr() and Q.shape == D.shape and Q.stride() == D.stride()
+    Q, ldq = _recall_table(Q, "Q")
+    D, ldd = (Q, ldq) if same else _recall_table(D, "D")
+    dev = Q.device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)   # noqa: E731
+    q_off_d, d_off_d, steps_d = up(qo), up(do), up(steps)
+    cand = cand.contiguous()
+    best = torch.empty((nq, K, 4), dtype=torch.int32, device=dev)
+    order = torch.empty((nq, K), dtype=torch.int32, device=dev)
+    block = torch.empty((nq, K, 32, 32), dtype=torch.int32, device=dev) if want_block else None
+    ws = torch.empty((nq + nd,), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _call("seq_match", lib.lpd_seq_match, _ptr(Q), ldq, nq, _ptr(q_off_d), qo.size - 1, _ptr(D), ldd, nd, _ptr(d_off_d), do.size - 1, Q.shape[1],
+          _ptr(cand), K, _ptr(steps_d), V, h, S, int(min_terms), _ptr(best), _ptr(order), _ptr(block), _ptr(ws), _stream())
+    return best, order, block
+
+
 def f64_to_f32(x64, out=None):
     """float64 CUDA tensor -> float32 (same shape), round to nearest even."""
     _req(x64, "x", torch.float64)
