@@ -9,6 +9,7 @@
 // lanes per point build the kNN operands exactly as knn_prep_pm4_kernel does (same summation order of the squared norm).
 // Everything stays exact fp32: these features feed the kNN, whose indices must be those of the fp32 reference.
 #include "lpd_common.h"
+#include "lpd_knn_ws.h"
 
 namespace {
 
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void lpdnet_front_kernel(FrontArgs g)
             cn += __shfl_xor(cn, mm, 64);
         }
         if (lane == 0) {
-            float* cnorm = g.tiles + nbt * 64;
+            float* cnorm = g.tiles + nbt * 64;                      // KnnWs::cnorm, rad, txmax behind ::cenp (lpd_knn_ws.h, cp = 32)
             cnorm[t] = cn;
             cnorm[nbt + t] = sqrtf(d2) * 1.0001f + 1e-30f;          // radius
             cnorm[2 * nbt + t] = bad ? INFINITY : nx;              // max |x|^2
@@ -236,11 +237,12 @@ extern "C" int lpd_lpdnet_front(const float* xyz, int ldx, const float* W1, cons
     LPD_CHECK_ARG((((uintptr_t)W2 | (uintptr_t)F0) & 15) == 0, "lpd_lpdnet_front: W2 and F0 must be 16-byte aligned");
     FrontArgs g{xyz, ldx, W1, s1, b1, W2, s2, b2, act == 0 ? 1.0f : (act == 1 ? 0.0f : slope), F0, nullptr, nullptr, nullptr, nullptr,
                 (long long)B * N, N, (N + 31) / 32};
-    if (knn_ws) {
-        void* xb = nullptr;
-        const int rc = lpd_knn_pm_layout(B, 64, N, k, knn_ws, &g.xx, &g.xp, &xb, &g.tiles);
-        if (rc != LPD_OK) return rc;
-        g.xb = reinterpret_cast<__bf16*>(xb);
+    if (knn_ws) {      // 64 channels and whole tiles: when the bound pass will run, its bf16 image comes from here (KnnRoute::prep_xb)
+        const KnnWs w = knn_ws_layout(B, 64, N, k, knn_ws);
+        g.xx = w.xx;
+        g.xp = w.xp;
+        g.xb = w.xb;
+        g.tiles = w.cenp;      // the kernel finds cnorm, rad and txmax behind the centroids itself
     }
     hipLaunchKernelGGL(lpdnet_front_kernel, dim3((unsigned)(g.M / FR_PTS)), dim3(256), 0, (hipStream_t)stream_, g);
     LPD_CHECK_LAUNCH("lpd_lpdnet_front");

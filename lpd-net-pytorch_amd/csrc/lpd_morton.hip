@@ -10,6 +10,7 @@
 // One 1024-thread block per cloud: bounding box -> 10 bits per axis -> 30-bit Morton code -> bitonic sort of 32-bit words
 // (top bits of the code | index) in registers / lane shuffles / LDS -> permuted copy of the cloud.  N <= 16384 (64 KiB of LDS).
 #include "lpd_common.h"
+#include "lpd_knn_ws.h"
 #include <math.h>
 
 namespace {
@@ -258,10 +259,7 @@ extern "C" int lpd_morton_sort_knn_applies(int N, int k)
 {
     static const bool on = lpd_debug("sort-knn", 1) != 0;
     if (!on || N % 32 != 0 || N < 64 || N > 16384 || k <= 0 || k > 64 || k > N) return 0;
-    float dummy[4];
-    float *xx = nullptr, *xp = nullptr, *tiles = nullptr;
-    void* xb = nullptr;
-    return lpd_knn_pm_layout(1, 3, N, k, dummy, &xx, &xp, &xb, &tiles) == LPD_OK && tiles != nullptr;
+    return knn_ws_layout(1, 3, N, k, nullptr).cenp != nullptr;      // the tile statistics have a reader: the best-first search is built
 }
 
 extern "C" int lpd_morton_sort_knn(const float* xyz, float* out, int32_t* perm, int B, int N, int k, float* knn_ws, void* stream_)
@@ -274,15 +272,7 @@ extern "C" int lpd_morton_sort_knn(const float* xyz, float* out, int32_t* perm, 
         lpd_set_error("lpd_morton_sort_knn: built for N %% 32 == 0, 64 <= N <= 16384 and the best-first search (N=%d k=%d)", N, k);
         return LPD_ERR_UNSUPPORTED;
     }
-    MortonWs ws;
-    float* tiles = nullptr;
-    void* xb = nullptr;
-    const int rc = lpd_knn_pm_layout(B, 3, N, k, knn_ws, &ws.xx, &ws.xp, &xb, &tiles);
-    if (rc != LPD_OK) return rc;
-    const size_t nbt = (size_t)B * (N / 32);
-    ws.cenp = tiles;
-    ws.cnorm = tiles + nbt * 4;
-    ws.rad = ws.cnorm + nbt;
-    ws.txmax = ws.rad + nbt;
+    const KnnWs w = knn_ws_layout(B, 3, N, k, knn_ws);
+    const MortonWs ws{w.xx, w.xp, w.cenp, w.cnorm, w.rad, w.txmax};
     return morton_dispatch(xyz, out, perm, B, N, stream, &ws);
 }
