@@ -780,6 +780,63 @@ int lpd_seq_match(const float* Q, int ldq, int nq, const int32_t* q_off, int SQ,
                   const int32_t* cand, int K, const int32_t* steps, int V, int h, int S, int min_terms,
                   int32_t* best, int32_t* order, int32_t* block, float* ws, void* stream);
 
+/*
+ * Pose-graph optimisation of a drive from its odometry and loop-closure edges (csrc/lpd_pgo.hip; arithmetic in csrc/lpd_pgo_math.h):
+ * the back end behind lpd_icp_pairs (Grisetti et al., "A tutorial on graph-based SLAM", 2010; Levenberg-Marquardt around block-Jacobi
+ * preconditioned conjugate gradients, as Dellaert et al., "Subgraph-preconditioned conjugate gradients", IROS 2010, and g2o's PCG
+ * solver do).  This comment is the specification, and lpd_pgo_math.h settles every detail it leaves open.  Everything is float64,
+ * every operation rounded once, nothing contracted, + - * / sqrt only, every comparison false on NaN.
+ *   G graphs, 1 <= G <= 65535; node_off [G+1], edge_off [G+1] int32 DEVICE arrays rising from 0 to V_total / E_total.  A graph has at
+ *            most 65536 nodes and 2^20 edges; an empty graph is legal and left alone; a graph whose offsets do not rise inside the
+ *            arrays is left alone as well (status "nothing to do", cost 0).  One workgroup solves one graph, in one launch.
+ *   pose     [V_total][12] IN and OUT: the top three rows (R | t) of the node-to-world matrix, the layout of lpd_drive_* and lpd_icp_pairs.
+ *   fixed    [V_total] uint8: a non-zero entry is a gauge node that never moves; a graph without one has its node 0 fixed.
+ *   edge     [E_total][2] int32 (i, j), LOCAL to the graph; meas [E_total][12] = Z_ij, the measured X_i^-1 X_j; weight [E_total][2] =
+ *            (w_rot, w_trans).  An edge is SKIPPED -- neither its measurement nor its weight is read further, it is counted in info --
+ *            when an end lies outside its graph, i == j, an entry of meas or weight is not finite, or a weight is negative.
+ *   csr_ptr  [V_total+1], csr_idx [2 E_total] int32, the CALLER's: row k lists the ends 2 e + end (e the edge's index in the arrays, end
+ *            0 for i, 1 for j) that touch node k (global number).  A node sums its edges in this order.  An entry that names no end
+ *            of a used edge of the node's graph at that node is passed over; nothing outside the arrays is read whatever the CSR holds.
+ * Residual of an edge: (R_e, t_e) = Z^-1 X_i^-1 X_j; r = (2 sgn(q_w) (q_x, q_y, q_z), t_e), q the unit quaternion of R_e by the branch
+ * of the largest of (trace, R00, R11, R22), a tie to the earlier one, sgn(0) = +1.  chi2_e = w_rot |r_rot|^2 + w_trans |r_t|^2; the
+ * cost is the sum over the used edges, in the fixed order below, of rho(chi2_e): rho(s) = s for huber = 0, and for huber = d > 0
+ * Huber's function of a = sqrt(s), s for a <= d and 2 d a - d^2 beyond, applied as the IRLS factor rho'(s) = d / a on both weights
+ * at each linearisation.  A node moves iff it is not fixed and a used edge touches it.
+ * Up to `outer` (0 .. 64) Levenberg-Marquardt trials.  A trial: linearise (only after an accepted trial) with the first-order Jacobians
+ * of lpd_pgo_jac; solve (H + lambda diag H) x = -g by at most cg_iters (1 .. 1024) iterations of conjugate gradients preconditioned by
+ * the damped 6 x 6 diagonal blocks, inverted by lpd_icp_math.h's unpivoted LDL^T, until r'z <= cg_tol^2 (r'z at the start), 0 <=
+ * cg_tol < 1; move every node on the right, R_k <- R_k dR(w_k), t_k <- t_k + R_k v_k, dR as in lpd_icp_pairs; evaluate the exact cost.
+ * The trial is ACCEPTED iff that cost is below the current one: lambda <- lambda / 10, and the solve has converged when the cost fell
+ * by no more than 1e-12 of itself.  Otherwise it is refused: the poses stay bit for bit and lambda <- max(10 lambda, 1e-9).  0 <=
+ * lambda0 <= 1e6.  A gradient with r'z = 0 at the start of a trial is convergence as well, and so is a solution with x'x <= 1e-24, which
+ * is not applied.
+ *   cost     [G][outer+1]: the cost before every trial and at the end; the slots behind the end of the solve repeat the last value.
+ *   chi2     [E_total]: the unweighted chi2_e at the final poses; -1 for a skipped edge.
+ *   info     [G][8] int32 = (status, trials accepted, trials refused, conjugate-gradient iterations in total, edges used, edges
+ *            skipped, nodes moved (0 when no trial was accepted), 0).  status: LPD_PGO_CONVERGED; LPD_PGO_ITERATIONS (the trials ran
+ *            out); LPD_PGO_NOTHING (no used edge or no node that moves); LPD_PGO_REFUSED: the first cost, a pivot of a diagonal block,
+ *            a solution or a moved pose was not positive / finite -- the solve ends there and the poses are those of the last
+ *            accepted trial, bit for bit (the input when none was accepted).
+ * Sums: thread t of the 256 takes the edges (nodes) e0 + t, e0 + t + 256, ... in ascending order into one partial; the 256 partials
+ * are added by a binary tree (t += t + 128, then 64, ...).  No float atomics: the same bits in every launch.  ws =
+ * lpd_pgo_workspace_bytes(V_total, E_total, G) bytes (0: bad sizes), 16-byte aligned, the caller's, one per call in flight, no
+ * state between calls.  Every decision is taken on the device; the call only enqueues.
+ */
+#define LPD_PGO_MAX_NODES 65536
+#define LPD_PGO_MAX_EDGES 1048576
+#define LPD_PGO_MAX_GRAPHS 65535
+#define LPD_PGO_MAX_OUTER 64
+#define LPD_PGO_MAX_CG 1024
+#define LPD_PGO_CONVERGED 0
+#define LPD_PGO_ITERATIONS 1
+#define LPD_PGO_NOTHING 2
+#define LPD_PGO_REFUSED 3
+long long lpd_pgo_workspace_bytes(long long V_total, long long E_total, int G);
+int lpd_pgo_solve(double* pose, const uint8_t* fixed, const int32_t* node_off, int V_total, const int32_t* edge, const double* meas,
+                  const double* weight, const int32_t* edge_off, int E_total, int G, const int32_t* csr_ptr, const int32_t* csr_idx,
+                  int outer, int cg_iters, double cg_tol, double lambda0, double huber, double* cost, double* chi2, int32_t* info,
+                  void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -1,7 +1,8 @@
 // lpd_icp_math.h -- the arithmetic of lpd_point_normals and lpd_icp_pairs (csrc/lpd_icp.hip): the unit normal of a neighbourhood
 // from its centred moments (the three-row form of lpd_feat_math.h's Jacobi), the fp32 transform of a point by a float64 pose, the
 // squared distance and the dmax decision of the correspondence search, the quantised point-to-plane row (J, r), the layout of the
-// 29 integer sums, and the float64 step: unpivoted LDL^T of the 6 x 6 normal equations and the pose update by a unit quaternion.
+// 29 integer sums, and the float64 step: unpivoted LDL^T of the 6 x 6 normal equations and the pose update by a unit quaternion
+// (lpd_icp_ldl6 and lpd_icp_dR, which csrc/lpd_pgo_math.h shares).
 // THIS HEADER IS THE DEFINITION of every detail that include/lpd_hip.h leaves open; tests/icp_ref.py restates every function in
 // numpy, and tests/test_icp_cpu.py compares the two value for value.
 //
@@ -164,14 +165,11 @@ LPD_ICP_FN void lpd_icp_terms(const int64_t* Ji, int64_t ri, int64_t* t)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the step, float64
 // ---------------------------------------------------------------------------------------------------------------------------------
-// H x = g by an unpivoted LDL^T, H = sum Ji Ji^T, g = sum Ji ri (the factor 1024^2 is on both sides: x is in radians and metres).
-// Returns 0 and leaves x alone when a pivot is not positive and finite.
-LPD_ICP_FN int lpd_icp_ldl(const int64_t* sums, double* x)
+// A x = g by an unpivoted LDL^T of a symmetric 6 x 6 A (both triangles filled).  Returns 0 and leaves x alone when a pivot is not
+// positive and finite.  lpd_pgo_math.h inverts its diagonal blocks with this routine as well.
+LPD_ICP_FN int lpd_icp_ldl6(const double (*A)[6], const double* g, double* x)
 {
-    double A[6][6], L[6][6], D[6], v[6], y[6];
-    int e = LPD_ICP_SUM_H;
-    for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = (double)sums[e++];
+    double L[6][6], D[6], v[6], y[6];
     for (int j = 0; j < 6; ++j) {
         double d = A[j][j];
         for (int k = 0; k < j; ++k) {
@@ -187,7 +185,7 @@ LPD_ICP_FN int lpd_icp_ldl(const int64_t* sums, double* x)
         }
     }
     for (int i = 0; i < 6; ++i) {      // L y = g, then z = y / D
-        double s = (double)sums[LPD_ICP_SUM_G + i];
+        double s = g[i];
         for (int k = 0; k < i; ++k) s = s - (L[i][k] * y[k]);
         y[i] = s;
     }
@@ -200,16 +198,35 @@ LPD_ICP_FN int lpd_icp_ldl(const int64_t* sums, double* x)
     return 1;
 }
 
-// pose [12] = (R | t) row-major <- (dR R | dR t + dt), dR the rotation of the unit quaternion (1, w / 2) / |(1, w / 2)|
-LPD_ICP_FN void lpd_icp_update(const double* x, double* pose)
+// H x = g, H = sum Ji Ji^T, g = sum Ji ri (the factor 1024^2 is on both sides: x is in radians and metres).  Returns 0 and leaves x
+// alone when a pivot is not positive and finite.
+LPD_ICP_FN int lpd_icp_ldl(const int64_t* sums, double* x)
+{
+    double A[6][6], g[6];
+    int e = LPD_ICP_SUM_H;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = (double)sums[e++];
+    for (int i = 0; i < 6; ++i) g[i] = (double)sums[LPD_ICP_SUM_G + i];
+    return lpd_icp_ldl6(A, g, x);
+}
+
+// dR [3][3] = the rotation of the unit quaternion (1, w / 2) / |(1, w / 2)|, w = x[0..2]
+LPD_ICP_FN void lpd_icp_dR(const double* x, double (*dR)[3])
 {
     const double hx = x[0] * 0.5, hy = x[1] * 0.5, hz = x[2] * 0.5;
     const double len = sqrt(((1.0 + (hx * hx)) + (hy * hy)) + (hz * hz));
     const double qw = 1.0 / len, qx = hx / len, qy = hy / len, qz = hz / len;
     const double xx = qx * qx, yy = qy * qy, zz = qz * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz, wx = qw * qx, wy = qw * qy, wz = qw * qz;
-    const double dR[3][3] = {{1.0 - (2.0 * (yy + zz)), 2.0 * (xy - wz), 2.0 * (xz + wy)},
-                             {2.0 * (xy + wz), 1.0 - (2.0 * (xx + zz)), 2.0 * (yz - wx)},
-                             {2.0 * (xz - wy), 2.0 * (yz + wx), 1.0 - (2.0 * (xx + yy))}};
+    dR[0][0] = 1.0 - (2.0 * (yy + zz)); dR[0][1] = 2.0 * (xy - wz); dR[0][2] = 2.0 * (xz + wy);
+    dR[1][0] = 2.0 * (xy + wz); dR[1][1] = 1.0 - (2.0 * (xx + zz)); dR[1][2] = 2.0 * (yz - wx);
+    dR[2][0] = 2.0 * (xz - wy); dR[2][1] = 2.0 * (yz + wx); dR[2][2] = 1.0 - (2.0 * (xx + yy));
+}
+
+// pose [12] = (R | t) row-major <- (dR R | dR t + dt), dR the rotation of the unit quaternion (1, w / 2) / |(1, w / 2)|
+LPD_ICP_FN void lpd_icp_update(const double* x, double* pose)
+{
+    double dR[3][3];
+    lpd_icp_dR(x, dR);
     double out[12];
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 4; ++j) out[4 * i + j] = ((dR[i][0] * pose[j]) + (dR[i][1] * pose[4 + j])) + (dR[i][2] * pose[8 + j]);

@@ -3,3 +3,4 @@ from ._lib import LIB_PATH, LpdHipError, load  # noqa: F401
 from . import ops  # noqa: F401
 from . import verify  # noqa: F401
 from . import sequence  # noqa: F401
+from . import posegraph  # noqa: F401

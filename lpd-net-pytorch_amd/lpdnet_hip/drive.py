@@ -267,11 +267,11 @@ def submaps_from_drive(points, lengths, poses, length=20.0, stride=10.0, num_poi
                 infos.append(info)
                 xforms.append(xform)
     sub = DriveSubmaps(x.view(W, 1, N, 3), torch.cat(infos), torch.cat(xforms), None, cleaned[0] if len(cleaned) == 1 else (cleaned or None))
-    sub.plan = plan
+    sub.plan, sub.frame = plan, frame
     return sub, plan.positions
 
 
 class DriveSubmaps(submap.Submaps):
     """submap.Submaps of a drive's windows, with `.plan` (the DrivePlan); `.cleaned` is the CleanedScans of the one window batch, a list
-    of them when there were several, or None."""
-    __slots__ = ("plan",)
+    of them when there were several, or None; `.frame` is the frame of the windows' points ("reference" or "world")."""
+    __slots__ = ("plan", "frame")

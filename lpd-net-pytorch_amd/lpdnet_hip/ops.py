@@ -1722,6 +1722,123 @@ def icp_pairs(a, b, normals_b, pairs, pose, dmax, min_inliers, scale_a=None, sca
 
 
 # ------------------------------------------------------------------------------------------------
+# pose-graph optimisation (csrc/lpd_pgo.hip)
+# ------------------------------------------------------------------------------------------------
+PGO_MAX_NODES, PGO_MAX_EDGES, PGO_MAX_GRAPHS = _lib.DEFINES["LPD_PGO_MAX_NODES"], _lib.DEFINES["LPD_PGO_MAX_EDGES"], _lib.DEFINES["LPD_PGO_MAX_GRAPHS"]
+PGO_MAX_OUTER, PGO_MAX_CG = _lib.DEFINES["LPD_PGO_MAX_OUTER"], _lib.DEFINES["LPD_PGO_MAX_CG"]
+PGO_CONVERGED, PGO_ITERATIONS, PGO_NOTHING, PGO_REFUSED = (_lib.DEFINES["LPD_PGO_" + n] for n in ("CONVERGED", "ITERATIONS", "NOTHING", "REFUSED"))
+PGO_MAX_LAMBDA0 = 1e6
+
+
+def _pgo_offsets(what, off, name, rows, limit):
+    """node_off / edge_off of pgo_solve: None (one graph), a host sequence of G + 1 integers rising from 0 to `rows` (checked here, no
+    graph longer than `limit`), or an int32 tensor (checked by the kernel: a graph whose offsets do not rise is left alone)
+    -> (host list or tensor, G)"""
+    if off is None:
+        if rows > limit:
+            raise ValueError(f"{what}: {rows} {name[:4]}s in one graph; at most {limit}")
+        return [0, rows], 1
+    if isinstance(off, torch.Tensor):
+        if off.dtype != torch.int32 or off.dim() != 1 or off.shape[0] < 2:
+            raise ValueError(f"{what}: {name} must be an int32 tensor of G + 1 >= 2 entries")
+        return off, off.shape[0] - 1
+    vals = [int(v) for v in off]
+    if len(vals) < 2 or vals[0] != 0 or vals[-1] != rows or any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{what}: {name} must rise from 0 to {rows} over G + 1 >= 2 entries")
+    if any(b - a > limit for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{what}: {name}: a graph is longer than {limit}")
+    return vals, len(vals) - 1
+
+
+def pgo_params(outer, cg_iters, cg_tol, lambda0, huber):
+    """the solver's parameters, validated -> (outer, cg_iters, cg_tol, lambda0, huber)"""
+    what = "pgo_solve"
+    for v, name, lo, hi in ((outer, "outer", 0, PGO_MAX_OUTER), (cg_iters, "cg_iters", 1, PGO_MAX_CG)):
+        if isinstance(v, bool) or not isinstance(v, int) and (not hasattr(v, "__index__") or int(v) != v) or not lo <= int(v) <= hi:
+            raise ValueError(f"{what}: {name}={v!r} (an integer in {lo} .. {hi})")
+    outer, cg_iters, cg_tol, lambda0, huber = int(outer), int(cg_iters), float(cg_tol), float(lambda0), float(huber)
+    if not 0.0 <= cg_tol < 1.0:
+        raise ValueError(f"{what}: cg_tol={cg_tol!r} outside [0, 1)")
+    if not 0.0 <= lambda0 <= PGO_MAX_LAMBDA0:
+        raise ValueError(f"{what}: lambda0={lambda0!r} outside [0, {PGO_MAX_LAMBDA0}]")
+    if not 0.0 <= huber < float("inf"):
+        raise ValueError(f"{what}: huber={huber!r} (finite, >= 0)")
+    return outer, cg_iters, cg_tol, lambda0, huber
+
+
+def pgo_csr(edge, node_off, edge_off, V):
+    """The node-to-edge lists lpd_pgo_solve walks, made on the device: csr_idx [2E] int32 = the ends 2 e + end sorted by their GLOBAL node
+    (a stable sort: a node's ends keep ascending order), an end outside its graph behind every node; csr_ptr [V + 1] int32.  edge
+    [E, 2] int32 local node numbers, node_off / edge_off [G + 1] int32 on the device.  Nothing is read back."""
+    E, G = edge.shape[0], node_off.shape[0] - 1
+    dev = edge.device
+    if E == 0:
+        return torch.zeros((V + 1,), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev)
+    gid = torch.bucketize(torch.arange(E, device=dev, dtype=torch.int32), edge_off[1:].contiguous(), right=True).clamp(max=G - 1)
+    off64 = node_off.to(torch.int64)
+    n0, n1 = off64[gid], off64[gid + 1]
+    ends = edge.to(torch.int64)
+    inside = (ends >= 0) & (ends < (n1 - n0)[:, None]) & (n0 >= 0)[:, None] & (n1 <= V)[:, None]
+    key = torch.where(inside, ends + n0[:, None], torch.full_like(ends, V)).reshape(2 * E)
+    skey, order = torch.sort(key, stable=True)
+    ptr = torch.searchsorted(skey, torch.arange(V + 1, device=dev, dtype=torch.int64))
+    return ptr.to(torch.int32), order.to(torch.int32)
+
+
+def pgo_solve(pose, edge, meas, weight, fixed=None, node_off=None, edge_off=None, outer=10, cg_iters=100, cg_tol=1e-6, lambda0=1e-4,
+              huber=0.0):
+    """Pose-graph optimisation of G graphs in one launch (lpd_pgo_solve; definition in include/lpd_hip.h).  pose [V, 12] float64 =
+    (R | t) row-major of every node (not written: the result is a new tensor), edge [E, 2] int32 = (i, j) local to the graph, meas
+    [E, 12] float64 = Z_ij, weight [E, 2] float64 = (w_rot, w_trans), fixed [V] uint8 or bool or None -- all on the device; node_off,
+    edge_off: None for one graph, host sequences of G + 1 integers, or int32 device tensors.
+    -> (pose [V, 12] float64, cost [G, outer + 1] float64, chi2 [E] float64, info [G, 8] int32).  Nothing is read back."""
+    what = "pgo_solve"
+    _tensor_arg(what, pose, "pose", torch.float64)
+    _tensor_arg(what, edge, "edge", torch.int32)
+    _tensor_arg(what, meas, "meas", torch.float64)
+    _tensor_arg(what, weight, "weight", torch.float64)
+    if fixed is not None and (not isinstance(fixed, torch.Tensor) or fixed.dtype not in (torch.uint8, torch.bool)):
+        raise TypeError(f"{what}: fixed: expected a uint8 or bool tensor")
+    if pose.dim() != 2 or pose.shape[1] != 12:
+        raise ValueError(f"{what}: pose must be [V, 12], got {tuple(pose.shape)}")
+    V = pose.shape[0]
+    if edge.dim() != 2 or edge.shape[1] != 2:
+        raise ValueError(f"{what}: edge must be [E, 2], got {tuple(edge.shape)}")
+    E = edge.shape[0]
+    if tuple(meas.shape) != (E, 12) or tuple(weight.shape) != (E, 2):
+        raise ValueError(f"{what}: meas must be [E, 12] and weight [E, 2] with E = {E}, got {tuple(meas.shape)} and {tuple(weight.shape)}")
+    if fixed is not None and tuple(fixed.shape) != (V,):
+        raise ValueError(f"{what}: fixed must be [V] = ({V},), got {tuple(fixed.shape)}")
+    if V > 1 << 30 or E > 1 << 29:
+        raise ValueError(f"{what}: V={V} E={E} exceed 2^30 nodes / 2^29 edges in all")
+    node_off, G = _pgo_offsets(what, node_off, "node_off", V, PGO_MAX_NODES)
+    edge_off, GE = _pgo_offsets(what, edge_off, "edge_off", E, PGO_MAX_EDGES)
+    if G != GE or not 1 <= G <= PGO_MAX_GRAPHS:
+        raise ValueError(f"{what}: node_off and edge_off describe {G} and {GE} graphs (one G, 1 .. {PGO_MAX_GRAPHS})")
+    outer, cg_iters, cg_tol, lambda0, huber = pgo_params(outer, cg_iters, cg_tol, lambda0, huber)
+    named = [(pose, "pose"), (edge, "edge"), (meas, "meas"), (weight, "weight"), (fixed, "fixed")]
+    named += [(t, n) for t, n in ((node_off, "node_off"), (edge_off, "edge_off")) if isinstance(t, torch.Tensor)]
+    _same_device(what, named)
+    lib = _lib.load()
+    dev = pose.device
+    if not isinstance(node_off, torch.Tensor):
+        node_off = torch.tensor(node_off, dtype=torch.int32, device=dev)
+    if not isinstance(edge_off, torch.Tensor):
+        edge_off = torch.tensor(edge_off, dtype=torch.int32, device=dev)
+    fixed = torch.zeros((V,), dtype=torch.uint8, device=dev) if fixed is None else fixed.to(torch.uint8)
+    pose = pose.contiguous().clone()
+    edge, meas, weight, fixed, node_off, edge_off = _contiguous(edge, meas, weight, fixed, node_off, edge_off)
+    csr_ptr, csr_idx = pgo_csr(edge, node_off, edge_off, V)
+    cost = torch.empty((G, outer + 1), dtype=torch.float64, device=dev)
+    chi2 = torch.empty((E,), dtype=torch.float64, device=dev)
+    info = torch.empty((G, 8), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(lib.lpd_pgo_workspace_bytes(V, E, G)), 16),), dtype=torch.uint8, device=dev)
+    _call(f"pgo_solve[G={G}]", lib.lpd_pgo_solve, _ptr(pose), _ptr(fixed), _ptr(node_off), V, _ptr(edge), _ptr(meas), _ptr(weight), _ptr(edge_off),
+          E, G, _ptr(csr_ptr), _ptr(csr_idx), outer, cg_iters, cg_tol, lambda0, huber, _ptr(cost), _ptr(chi2), _ptr(info), _ptr(ws), _stream())
+    return pose, cost, chi2, info
+
+
+# ------------------------------------------------------------------------------------------------
 # training-path wrappers (csrc/lpd_train.hip)
 # ------------------------------------------------------------------------------------------------
 class BNStats:
