@@ -837,6 +837,70 @@ int lpd_pgo_solve(double* pose, const uint8_t* fixed, const int32_t* node_off, i
                   int outer, int cg_iters, double cg_tol, double lambda0, double huber, double* cost, double* chi2, int32_t* info,
                   void* ws, void* stream);
 
+/*
+ * Pairwise-consistent loop closures: which loops of a graph to hand to lpd_pgo_solve (csrc/lpd_loops.hip; arithmetic in
+ * csrc/lpd_loops_math.h; Mangelson et al., "Pairwise consistent measurement set maximization for robust multi-robot map merging", ICRA
+ * 2018).  Two loops agree if the cycle through both and the odometry between their ends closes within its uncertainty; a large set of
+ * mutually agreeing loops is kept.  This comment is the specification, and lpd_loops_math.h settles every detail it leaves open.
+ * Everything is float64, every operation rounded once, nothing contracted, + - * / sqrt only, every comparison false on NaN.
+ *   G graphs, 1 <= G <= 65535; node_off [G+1], loop_off [G+1] int32 DEVICE arrays rising from 0 to V_total / P_total, as lpd_pgo_solve
+ *            takes them.  A graph holds at most LPD_LOOPS_MAX = 4096 loops.  A row that lies in no graph whose offsets rise inside the
+ *            arrays is treated as an invalid loop.
+ *   pose     [V_total][12]: the nodes' start, (R | t) row-major.  Read, never written.  The nodes of a graph are consecutive windows, as
+ *            the odometry edges link them: between nodes i and k lie |i - k| odometry steps.
+ *   edge     [P_total][2] int32 (i, j), LOCAL to the graph; meas [P_total][12] = Z, the measured X_i^-1 X_j; weight [P_total][2] =
+ *            (w_rot, w_trans): the loops, as lpd_pgo_solve takes them.
+ *   w_or, w_ot  > 0: the weights of ONE odometry step between consecutive nodes; gate >= 0, finite.
+ * A loop is VALID iff lpd_pgo_solve would use it (both ends inside the graph and different, meas and weight finite, weights >= 0) and
+ * both its weights are > 0.  An invalid loop has an all-zero row and is never chosen.
+ * Pair statistic of the valid loops a < b (local numbers) of one graph:
+ *   E     = Z_a (X_ja^-1 X_jb) Z_b^-1 (X_ib^-1 X_ia), evaluated as ((Z_a T1) T2), T1 = X_ja^-1 X_jb, T2 = (X_ib Z_b)^-1 X_ia;
+ *   r     = (2 sgn(q_w) (q_x, q_y, q_z) of R_E, t_E), the quaternion by lpd_pgo_solve's rule;
+ *   n_i   = |i_a - i_b|, n_j = |j_a - j_b|;  c_i^2 = |t(X_ia) - t(X_ib)|^2, c_j^2 = |t(X_ja) - t(X_jb)|^2;
+ *   var_r = 1/w_rot,a + 1/w_rot,b + (n_i + n_j) / w_or;
+ *   var_t = 1/w_trans,a + 1/w_trans,b + (n_i + n_j) / w_ot + (n_i c_i^2 + n_j c_j^2) / w_or   (the last term is the lever arm: a heading
+ *           error at the start of an odometry segment swings the whole chord);
+ *   the pair is CONSISTENT iff |r_rot|^2 / var_r + |r_t|^2 / var_t <= gate.
+ * Bit (a, b) and bit (b, a) are both the decision for (min, max): the matrix is symmetric by construction; the diagonal is 0.
+ *
+ * lpd_loop_consistency:
+ *   adj      [P_total][ldw] uint64: bit b (the LOCAL loop number; bit b & 63 of word b >> 6) of row a.  Every word is written, zeros
+ *            beyond the graph.  1 <= ldw <= 64 is the caller's stride.  A word is one __ballot of 64 lanes (lanes = columns) stored once.
+ *   degree   [P_total] int32 = the row's popcount for a valid loop, and -1 for an invalid one: lpd_loop_select needs nothing else to
+ *            tell a valid loop that agrees with no other from an invalid one.
+ *   A graph with more than 64 ldw loops is left alone: its rows are zero, its degrees -1, and lpd_loop_select reports
+ *   LPD_LOOPS_TOO_MANY.  No atomics of any kind.
+ *
+ * lpd_loop_select takes adj and degree as they are (bits of columns outside the graph, of invalid loops and of the diagonal are masked):
+ *   seeds    1 .. LPD_LOOPS_MAX_SEEDS = 64; seed s (from 0) of a graph is the valid loop with the (s+1)-th largest degree, ties to the
+ *            lower number, found on the device.  A graph with fewer valid loops runs fewer seeds.
+ *   From a seed: C = {seed}, cand = adj[seed].  While cand is not empty: take the u in cand with the largest popcount(adj[u] & cand),
+ *   ties to the lowest u; C += u; cand &= adj[u].  Each choice is a block-wide integer maximum of (count << 12) | (4095 - u).  One
+ *   workgroup per (graph, seed); no barrier across workgroups of any kind; every loop is bounded by a loop count.  The winner among the
+ *   seeds -- the largest C, ties to the lower s -- is chosen in a second small launch enqueued by the same call.  The greedy set is
+ *   always maximal (no further loop is consistent with all of it), not always maximum.
+ *   accepted [P_total] uint8: 1 for the loops of the winner, 0 for every other loop of a graph; rows of no graph are not written.
+ *   info     [G][8] int32 = (status, loops valid, loops chosen, seeds run, the winning seed's loop (-1: none), consistent pairs, 0, 0).
+ *            status: LPD_LOOPS_OK; LPD_LOOPS_NOTHING (no valid loop, or offsets that do not rise inside the arrays); LPD_LOOPS_TOO_FEW
+ *            (the winner is smaller than min_size >= 1: nothing accepted, 0 chosen); LPD_LOOPS_TOO_MANY (more than 64 ldw loops).
+ *   ws       lpd_loop_select_workspace_bytes(G, seeds, ldw) bytes (0: bad sizes), 16-byte aligned, the caller's, one per call in
+ *            flight, no state between calls.
+ * The same bits in every launch.  Both calls only enqueue; nothing is read back.
+ */
+#define LPD_LOOPS_MAX 4096
+#define LPD_LOOPS_MAX_SEEDS 64
+#define LPD_LOOPS_MAX_GRAPHS 65535
+#define LPD_LOOPS_OK 0
+#define LPD_LOOPS_NOTHING 1
+#define LPD_LOOPS_TOO_FEW 2
+#define LPD_LOOPS_TOO_MANY 3
+int lpd_loop_consistency(const double* pose, const int32_t* node_off, int V_total, const int32_t* edge, const double* meas,
+                         const double* weight, const int32_t* loop_off, int P_total, int G, double w_or, double w_ot, double gate,
+                         uint64_t* adj, int ldw, int32_t* degree, void* stream);
+long long lpd_loop_select_workspace_bytes(int G, int seeds, int ldw);
+int lpd_loop_select(const uint64_t* adj, int ldw, const int32_t* degree, const int32_t* loop_off, int P_total, int G, int seeds,
+                    int min_size, uint8_t* accepted, int32_t* info, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

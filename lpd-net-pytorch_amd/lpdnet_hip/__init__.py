@@ -4,3 +4,4 @@ from . import ops  # noqa: F401
 from . import verify  # noqa: F401
 from . import sequence  # noqa: F401
 from . import posegraph  # noqa: F401
+from . import consistency  # noqa: F401

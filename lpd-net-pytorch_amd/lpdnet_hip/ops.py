@@ -3,6 +3,7 @@ autograd lives in autograd.py.  Every op requires CUDA fp32 tensors and raises o
 there is deliberately no CPU or eager-PyTorch fallback.
 """
 import ctypes
+import numbers
 import os
 
 import torch
@@ -1836,6 +1837,120 @@ def pgo_solve(pose, edge, meas, weight, fixed=None, node_off=None, edge_off=None
     _call(f"pgo_solve[G={G}]", lib.lpd_pgo_solve, _ptr(pose), _ptr(fixed), _ptr(node_off), V, _ptr(edge), _ptr(meas), _ptr(weight), _ptr(edge_off),
           E, G, _ptr(csr_ptr), _ptr(csr_idx), outer, cg_iters, cg_tol, lambda0, huber, _ptr(cost), _ptr(chi2), _ptr(info), _ptr(ws), _stream())
     return pose, cost, chi2, info
+
+
+# ------------------------------------------------------------------------------------------------
+# pairwise-consistent loop closures (csrc/lpd_loops.hip)
+# ------------------------------------------------------------------------------------------------
+LOOPS_MAX, LOOPS_MAX_SEEDS, LOOPS_MAX_GRAPHS = _lib.DEFINES["LPD_LOOPS_MAX"], _lib.DEFINES["LPD_LOOPS_MAX_SEEDS"], _lib.DEFINES["LPD_LOOPS_MAX_GRAPHS"]
+LOOPS_OK, LOOPS_NOTHING, LOOPS_TOO_FEW, LOOPS_TOO_MANY = (_lib.DEFINES["LPD_LOOPS_" + n] for n in ("OK", "NOTHING", "TOO_FEW", "TOO_MANY"))
+LOOPS_MAX_LDW = LOOPS_MAX // 64
+
+
+def _loops_int(what, v, name, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) and (not hasattr(v, "__index__") or int(v) != v) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what}: {name}={v!r} (an integer in {lo} .. {hi})")
+    return int(v)
+
+
+def _loops_ldw(what, ldw, loop_off, P):
+    """the stride of the bit rows: the caller's (1 .. 64), or the least that holds the longest graph of host offsets (64 for a tensor)"""
+    if ldw is not None:
+        return _loops_int(what, ldw, "ldw", 1, LOOPS_MAX_LDW)
+    if isinstance(loop_off, torch.Tensor):
+        return LOOPS_MAX_LDW
+    return max(1, max(-(-(b - a) // 64) for a, b in zip(loop_off, loop_off[1:])))
+
+
+def loop_params(w_or, w_ot, gate):
+    """the odometry weights of one step and the gate, validated -> (w_or, w_ot, gate)"""
+    what = "loop_consistency"
+    out = []
+    for v, name in ((w_or, "w_or"), (w_ot, "w_ot")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 < float(v) < float("inf"):
+            raise ValueError(f"{what}: {name}={v!r} (a finite number > 0)")
+        out.append(float(v))
+    if isinstance(gate, bool) or not isinstance(gate, numbers.Real) or not 0.0 <= float(gate) < float("inf"):
+        raise ValueError(f"{what}: gate={gate!r} (a finite number >= 0)")
+    return out[0], out[1], float(gate)
+
+
+def loop_consistency(pose, edge, meas, weight, w_or, w_ot, gate, node_off=None, loop_off=None, ldw=None):
+    """Which loops of a graph agree pairwise (lpd_loop_consistency; definition in include/lpd_hip.h).  pose [V, 12] float64 = the nodes'
+    start, edge [P, 2] int32 local to the graph, meas [P, 12] float64, weight [P, 2] float64 = the loops as posegraph.loop_edges returns
+    them -- all on the device; w_or, w_ot > 0 the odometry weights of one step, gate >= 0 and finite; node_off, loop_off: None for one graph, host
+    sequences of G + 1 integers, or int32 device tensors; ldw: the stride of a bit row in words, 1 .. 64 (None: what the longest graph
+    needs).  -> (adj [P, ldw] int64 = the uint64 words' bit patterns, degree [P] int32, -1 for an invalid loop).  Nothing is read back."""
+    what = "loop_consistency"
+    _tensor_arg(what, pose, "pose", torch.float64)
+    _tensor_arg(what, edge, "edge", torch.int32)
+    _tensor_arg(what, meas, "meas", torch.float64)
+    _tensor_arg(what, weight, "weight", torch.float64)
+    if pose.dim() != 2 or pose.shape[1] != 12:
+        raise ValueError(f"{what}: pose must be [V, 12], got {tuple(pose.shape)}")
+    if edge.dim() != 2 or edge.shape[1] != 2:
+        raise ValueError(f"{what}: edge must be [P, 2], got {tuple(edge.shape)}")
+    V, P = pose.shape[0], edge.shape[0]
+    if tuple(meas.shape) != (P, 12) or tuple(weight.shape) != (P, 2):
+        raise ValueError(f"{what}: meas must be [P, 12] and weight [P, 2] with P = {P}, got {tuple(meas.shape)} and {tuple(weight.shape)}")
+    if V > 1 << 30 or P > 1 << 24:
+        raise ValueError(f"{what}: V={V} P={P} exceed 2^30 nodes / 2^24 loops in all")
+    w_or, w_ot, gate = loop_params(w_or, w_ot, gate)
+    node_off, G = _pgo_offsets(what, node_off, "node_off", V, PGO_MAX_NODES)
+    loop_off, GP = _pgo_offsets(what, loop_off, "loop_off", P, LOOPS_MAX)
+    if G != GP or not 1 <= G <= LOOPS_MAX_GRAPHS:
+        raise ValueError(f"{what}: node_off and loop_off describe {G} and {GP} graphs (one G, 1 .. {LOOPS_MAX_GRAPHS})")
+    ldw = _loops_ldw(what, ldw, loop_off, P)
+    named = [(pose, "pose"), (edge, "edge"), (meas, "meas"), (weight, "weight")]
+    named += [(t, n) for t, n in ((node_off, "node_off"), (loop_off, "loop_off")) if isinstance(t, torch.Tensor)]
+    _same_device(what, named)
+    lib = _lib.load()
+    dev = pose.device
+    if not isinstance(node_off, torch.Tensor):
+        node_off = torch.tensor(node_off, dtype=torch.int32, device=dev)
+    if not isinstance(loop_off, torch.Tensor):
+        loop_off = torch.tensor(loop_off, dtype=torch.int32, device=dev)
+    pose, edge, meas, weight, node_off, loop_off = _contiguous(pose, edge, meas, weight, node_off, loop_off)
+    adj = torch.empty((P, ldw), dtype=torch.int64, device=dev)
+    degree = torch.empty((P,), dtype=torch.int32, device=dev)
+    _call(f"loop_consistency[G={G}]", lib.lpd_loop_consistency, _ptr(pose), _ptr(node_off), V, _ptr(edge), _ptr(meas), _ptr(weight), _ptr(loop_off),
+          P, G, w_or, w_ot, gate, _ptr(adj), ldw, _ptr(degree), _stream())
+    return adj, degree
+
+
+def loop_select(adj, degree, loop_off=None, seeds=8, min_size=3):
+    """A large set of mutually consistent loops per graph, greedily from `seeds` seeds (lpd_loop_select; definition in include/lpd_hip.h).
+    adj [P, ldw] int64 (the uint64 words' bit patterns) and degree [P] int32 as loop_consistency returns them, or hand-made, on the
+    device; loop_off as for loop_consistency; seeds 1 .. 64; min_size >= 1.  -> (accepted [P] uint8, info [G, 8] int32 = (status, loops
+    valid, loops chosen, seeds run, the winning seed's loop, consistent pairs, 0, 0)).  Nothing is read back."""
+    what = "loop_select"
+    _tensor_arg(what, adj, "adj", torch.int64)
+    _tensor_arg(what, degree, "degree", torch.int32)
+    if adj.dim() != 2 or not 1 <= adj.shape[1] <= LOOPS_MAX_LDW:
+        raise ValueError(f"{what}: adj must be [P, ldw] with ldw in 1 .. {LOOPS_MAX_LDW}, got {tuple(adj.shape)}")
+    P, ldw = adj.shape
+    if tuple(degree.shape) != (P,):
+        raise ValueError(f"{what}: degree must be [P] = ({P},), got {tuple(degree.shape)}")
+    if P > 1 << 24:
+        raise ValueError(f"{what}: P={P} exceeds 2^24 loops in all")
+    seeds = _loops_int(what, seeds, "seeds", 1, LOOPS_MAX_SEEDS)
+    min_size = _loops_int(what, min_size, "min_size", 1, (1 << 31) - 1)
+    loop_off, G = _pgo_offsets(what, loop_off, "loop_off", P, 1 << 24)      # a graph over 64 ldw loops is the kernel's to refuse
+    if not 1 <= G <= LOOPS_MAX_GRAPHS:
+        raise ValueError(f"{what}: loop_off describes {G} graphs (1 .. {LOOPS_MAX_GRAPHS})")
+    named = [(adj, "adj"), (degree, "degree")] + ([(loop_off, "loop_off")] if isinstance(loop_off, torch.Tensor) else [])
+    _same_device(what, named)
+    lib = _lib.load()
+    dev = adj.device
+    if not isinstance(loop_off, torch.Tensor):
+        loop_off = torch.tensor(loop_off, dtype=torch.int32, device=dev)
+    adj, degree, loop_off = _contiguous(adj, degree, loop_off)
+    accepted = _zeros((P,), torch.uint8, dev)
+    info = torch.empty((G, 8), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(lib.lpd_loop_select_workspace_bytes(G, seeds, ldw)), 16),), dtype=torch.uint8, device=dev)
+    _call(f"loop_select[G={G}]", lib.lpd_loop_select, _ptr(adj), ldw, _ptr(degree), _ptr(loop_off), P, G, seeds, min_size, _ptr(accepted), _ptr(info),
+          _ptr(ws), _stream())
+    return accepted, info
 
 
 # ------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ back end that uses it: a graph whose nodes are the windows' reference poses, who
     od = posegraph.odometry_edges(node_poses)                                      # (edge [V-1, 2], meas [V-1, 12], weight [V-1, 2])
     lp = posegraph.loop_edges(rf, pairs)                                           # pair (a, b) -> edge (i = b, j = a, Z = rf.matrix())
     res = posegraph.PoseGraph(node_poses, od, lp).optimize(outer=20, huber=3.0)
+    res = posegraph.close_loops(sub, poses, rf, pairs, consistent=True)            # only a pairwise-consistent set of the loops (consistency.py)
 
 Every launch gives the same bits, equal to the numpy restatement (tests/pgo_ref.py).  Nothing is read back.  No CPU fallback.
 """
@@ -133,11 +134,12 @@ class PoseGraphResult:
     """What PoseGraph.optimize returns, all on the device: poses [V, 3, 4] float64; positions [V, 2] float64 = their x and y, what
     places.training_lists, places.evaluation_truth and TupleBank.from_positions take; cost [outer + 1] float64 = the cost before every
     trial and at the end; chi2 [E] float64 = every edge's final unweighted chi-squared, -1 for a skipped edge; info [8] int32 =
-    (status, accepted, refused, CG iterations, edges used, edges skipped, nodes moved, 0); converged = a 0-d bool tensor."""
-    __slots__ = ("poses", "cost", "chi2", "info")
+    (status, accepted, refused, CG iterations, edges used, edges skipped, nodes moved, 0); converged = a 0-d bool tensor; selection =
+    the consistency.LoopConsistency behind close_loops(consistent=...), None otherwise."""
+    __slots__ = ("poses", "cost", "chi2", "info", "selection")
 
-    def __init__(self, poses, cost, chi2, info):
-        self.poses, self.cost, self.chi2, self.info = poses, cost, chi2, info
+    def __init__(self, poses, cost, chi2, info, selection=None):
+        self.poses, self.cost, self.chi2, self.info, self.selection = poses, cost, chi2, info, selection
 
     @property
     def positions(self):
@@ -190,11 +192,14 @@ class PoseGraph:
         return PoseGraphResult(pose.reshape(-1, 3, 4), cost[0], chi2, info[0])
 
 
-def close_loops(sub, poses, loops, pairs=None, odometry_weights=ODOMETRY_WEIGHTS, loop_weights=LOOP_WEIGHTS, accepted=None, fixed=None, **solver):
+def close_loops(sub, poses, loops, pairs=None, odometry_weights=ODOMETRY_WEIGHTS, loop_weights=LOOP_WEIGHTS, accepted=None, fixed=None,
+                consistent=None, **solver):
     """A drive's windows corrected by its loop closures -> PoseGraphResult.  sub: the drive.DriveSubmaps of submaps_from_drive(...,
     frame="reference"); poses: the drive's input poses, as drive takes them (the nodes start at the poses of sub.plan.ref, the windows'
     reference scans); loops: verify.refine_pairs' Refinement of `pairs` [P, 2] = (window a, window b), or refine_candidates'
-    Verification with pairs = its topk_idx; **solver goes to PoseGraph.optimize.  Nothing is read back."""
+    Verification with pairs = its topk_idx; consistent: None hands every loop to the solver; a consistency.ConsistencySearch (True: the
+    default one) keeps a large set of pairwise-consistent loops, judged at the nodes' start with odometry_weights, and the result carries
+    the LoopConsistency as .selection; **solver goes to PoseGraph.optimize.  Nothing is read back."""
     from . import drive
     what = "close_loops"
     if not isinstance(sub, drive.DriveSubmaps):
@@ -208,9 +213,22 @@ def close_loops(sub, poses, loops, pairs=None, odometry_weights=ODOMETRY_WEIGHTS
         raise ValueError(f"{what}: odometry_weights and loop_weights are (w_rot, w_trans)")
     _weights(what, *odometry_weights)
     _weights(what, *loop_weights)
+    search = None
+    if consistent is not None and consistent is not False:
+        from . import consistency
+        search = consistency.ConsistencySearch() if consistent is True else consistent
+        if not isinstance(search, consistency.ConsistencySearch):
+            raise TypeError(f"{what}: consistent must be None, True or a consistency.ConsistencySearch, got {type(consistent).__name__}")
     plan = sub.plan
     p = drive._poses(poses, plan.ref.device, what)
     nodes = p[plan.ref.to(torch.int64).clamp(min=0)]
     od = odometry_edges(nodes, None, *odometry_weights)
     lp = loop_edges(loops, pairs, accepted, *loop_weights)
-    return PoseGraph(nodes, od, lp, fixed=fixed).optimize(**solver)
+    if search is None:
+        return PoseGraph(nodes, od, lp, fixed=fixed).optimize(**solver)
+    graph = PoseGraph(nodes, od, lp, fixed=fixed)      # the whole graph's arguments are checked before the selection runs
+    selection = consistency.consistent_loops(nodes, lp, tuple(odometry_weights), search)
+    graph.edges[1] = consistency.filter_loops(lp, selection.accepted)
+    res = graph.optimize(**solver)
+    res.selection = selection
+    return res
