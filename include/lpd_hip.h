@@ -901,6 +901,70 @@ long long lpd_loop_select_workspace_bytes(int G, int seeds, int ldw);
 int lpd_loop_select(const uint64_t* adj, int ldw, const int32_t* degree, const int32_t* loop_off, int P_total, int G, int seeds,
                     int min_size, uint8_t* accepted, int32_t* info, void* ws, void* stream);
 
+/*
+ * The drive map (csrc/lpd_map.hip; arithmetic in csrc/lpd_map_math.h): what lpd_pgo_solve's corrected nodes are FOR.  lpd_drive_correct
+ * carries the nodes' correction to every scan of the drive, so that the corrected drive goes back into lpd_drive_*; lpd_map_insert
+ * averages posed scans into one global voxel grid kept as a hash table -- the product a second lap or session is localised against, and
+ * the one quality measure of a loop closure that needs no ground truth: the occupied-cell count falls when the laps coincide.  This
+ * comment is the specification, and lpd_map_math.h settles every detail it leaves open.  No read-back.
+ *
+ * lpd_drive_correct.  Float64; every operation rounded once, nothing contracted; dot products ((a0*b0) + (a1*b1)) + (a2*b2); only
+ * + - * / sqrt.
+ *   poses      [S][12] float64, the drive's input poses (R | t), the layout of lpd_drive_*
+ *   D          [S] int64, the distance of lpd_drive_steps + cumsum, units of 2^-16 m
+ *   node_scan  [V] int32, non-decreasing, each in [0, S): the scans that are nodes (a plan's `ref` without the empty windows)
+ *   node_pose  [V][12] float64, the optimised nodes
+ *   out        [S][12] float64;  info [2] int32, ADDED to: scans made from the nodes, scans passed through
+ *  1 Bracket.   a = the last node with node_scan[a] <= i, b = a + 1 the first with node_scan[b] > i; of equal entries a is the last.
+ *  2 Node.      i == node_scan[a]: out_i = node_pose[a], a bit copy.
+ *  3 Candidate. From a node n at scan s: rel = (R_s^T R_i, R_s^T (t_i - t_s)) of the INPUT poses, the difference first; X' = node_pose[n]
+ *               composed with rel (R' = R_n R_rel, t' = R_n t_rel + t_n).  The input odometry stays rigid around the node.
+ *  4 One.       Before the first node or behind the last the one candidate is the result.
+ *  5 Weight.    alpha = (double)(D_i - D_a) / (double)(D_b - D_a), D_a = D[node_scan[a]]; 0 when the denominator is 0.
+ *  6 Blend.     t = t_A + alpha (t_B - t_A).  q_A, q_B = the candidates' quaternions by the largest of (trace, R00, R11, R22)
+ *               (lpd_pgo_quat); q_B negated when the four-term dot product is negative; q = q_A + alpha (q_B - q_A), each entry divided by
+ *               the square root of the squared norm; R by the usual quadratic form (lpd_map_blend writes it out).
+ *  7 Pass.      A scan whose own input pose is not finite, whose bracket involves an input or optimised pose that is not finite, or
+ *               whose bracket is not one (node_scan[a] outside [0, i], node_scan[b] outside (i, S)) gets its input pose as a bit copy and
+ *               is counted in info[1].  Nothing outside the tables is read, whatever node_scan holds.
+ * One thread per scan, a binary search over node_scan, no atomics beyond the two counters: the same bits in every launch.
+ * Limits: 1 <= S <= 2^22, 1 <= V <= S.
+ *
+ * lpd_map_insert.  points / ld / rows / offsets / poses / S as lpd_drive_rows takes them; the scans scan0 .. scan1-1 are inserted.
+ *   origin     [3] float64 on the device;  inv_cell fp32 = the caller's 1.0f / cell, 1/16 .. 1024 (a cell of 2^-10 .. 16 m)
+ *   keys       [capacity] int64, -1 = an empty slot;  acc [capacity][4] int64 = (Sx, Sy, Sz, m): 32 bytes, a slot's four adds land in
+ *              one sector.  capacity a power of two, 16 .. 2^36.  The table is the caller's, and clearing it is the caller's fill.
+ *   info       [4] int64, ADDED to: rows inserted, rows dropped, rows lost to a full table, cells created
+ *  1 World row. Exactly lpd_drive_rows with frame = 0 and t_ref = origin: M = R_i, u = t_i - origin in float64, the twelve numbers rounded
+ *               to fp32 once; w_c = (((M_c0*x) + (M_c1*y)) + (M_c2*z)) + u_c in fp32.  The float64 subtraction first is what keeps a UTM
+ *               northing of 5.7e6 usable (there an fp32 ulp is 0.5 m).
+ *  2 Cell.      f_c = floorf(w_c * inv_cell); a row with an f_c that is NaN or outside [-2^20, 2^20) is dropped and counted; q_c = (int)
+ *               f_c; key = (qx + 2^20) | (qy + 2^20) << 21 | (qz + 2^20) << 42: 63 bits, never -1, ascending key = z-major order.
+ *  3 Value.     U_c = (int64) rint((double) w_c * 65536.0), half to even; conversion and product are exact.  |U_c| < 2^41, so the sums of
+ *               fewer than 2^22 rows in one cell stay inside an int64 anywhere, of fewer than 2^32 rows within 32 km of the origin.
+ *  4 Slot.      The first slot is mix(key) & (capacity - 1), mix = the finaliser of splitmix64 (lpd_map_mix); linear probing with wrap-
+ *               around, at most min(128, capacity) probes; compare-and-swap on the key word; on insert or match three 64-bit integer
+ *               adds of U and one of 1.  An insert adds 1 to info[3]; running out of probes adds the row to info[2] and the row is lost.
+ *  5 Addresses. The only address that comes from data is the masked slot.  Nothing is read unless 0 <= offsets[scan0] <=
+ *               offsets[scan1] <= rows; the rows are taken in chunks of 1024 input rows, and a chunk whose part of the offsets table is
+ *               not one (lpd_map_chunk_ok: it descends, or does not hold the chunk's rows) is not read and its rows count as dropped.
+ * What is and is not deterministic: WHICH slot a key lands in depends on timing.  The mapping key -> (Sx, Sy, Sz, m) does not, as long
+ * as info[2] stays 0: integer sums are exact in any order and a key is inserted exactly once.  With info[2] > 0 the table's content is
+ * unspecified beyond inserted + dropped + lost == rows of the call; the caller takes a larger table and starts over.  Several calls
+ * (batches of scans, a second drive, several streams on several tables) give the same mapping as one call.  By default the rows of a
+ * chunk are summed per workgroup in LDS first and each distinct key of the chunk goes to the table once; LPD_DEBUG=map-direct sends every
+ * row straight to the table.  Both add the same integers to the same keys.  Integer atomics only; no barrier across workgroups.
+ *
+ * lpd_map_rehash inserts every occupied slot of a table (keys_in, acc_in, capacity_in) into another one by rule 4, sums and counts as
+ * they are: how a table grows.  info as above (rows inserted = the cells' counts m, cells created).
+ */
+int lpd_drive_correct(const double* poses, const long long* D, int S, const int32_t* node_scan, const double* node_pose, int V, double* out,
+                      int32_t* info, void* stream);
+int lpd_map_insert(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,
+                   const double* origin, float inv_cell, long long* keys, long long* acc, long long capacity, long long* info, void* stream);
+int lpd_map_rehash(const long long* keys_in, const long long* acc_in, long long capacity_in, long long* keys, long long* acc,
+                   long long capacity, long long* info, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -1,0 +1,288 @@
+// lpd_map.hip -- the drive map: the nodes' correction of a pose graph carried to every scan, and posed scans averaged into one global
+// voxel grid kept as a hash table.  Definition: include/lpd_hip.h; arithmetic: lpd_map_math.h.
+//
+//   correct  one thread per scan: a binary search over node_scan, two rigid candidates in float64, their blend.  The only atomics are
+//            the two counters (the compiler folds a wave's adds into one).
+//   insert   grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, MP_T = 256 threads.  A chunk is loaded as lpd_drive_rows loads it
+//            (ld == 3: a flat copy with 16-byte accesses on the aligned body; ld == 4 with an aligned table: one 16-byte load a row), the
+//            fp32 poses of its scans are made once per workgroup in float64 (MP_CAP = 64 of them; a chunk of more scans lets every row
+//            make its own, the same bits), and every row becomes (key, Ux, Uy, Uz).
+//              aggregated form (the default): the rows of the chunk are summed in a table of LPD_MAP_LDS_SLOTS slots in LDS first --
+//              consecutive rows of a scan line fall into the same few cells -- with 64-bit LDS integer atomics and the same key; each
+//              distinct key of the chunk then goes to the caller's table with ONE compare-and-swap probe sequence and four 64-bit adds.
+//              A row that finds no LDS slot in LPD_MAP_LDS_PROBES probes goes straight to the caller's table.
+//              direct form (LPD_DEBUG=map-direct): every row straight to the caller's table.
+//            Both forms add the same integers to the same keys, so the extracted map is the same.
+//   rehash   one thread per slot of an old table: its (key, sums) inserted into a new one.
+// Integer atomics only: a sum does not depend on the order of its terms.  WHICH slot a key lands in depends on timing; the mapping
+// key -> (Sx, Sy, Sz, m) does not.  No barrier across workgroups.  The only address that comes from data is a slot index, masked by
+// capacity - 1; every index into offsets, poses and points is checked against its table first.
+#include <math.h>
+
+#include "lpd_common.h"
+#include "lpd_map_math.h"
+
+namespace {
+
+constexpr int MP_T = 256;
+constexpr int MP_CH = LPD_MAP_CHUNK;
+constexpr int MP_R = MP_CH / MP_T;      // rows per thread
+constexpr int MP_CAP = 64;              // poses a workgroup keeps in LDS
+constexpr int MP_LS = LPD_MAP_LDS_SLOTS;
+typedef unsigned long long u64;
+
+__global__ __launch_bounds__(MP_T) void correct_kernel(const double* __restrict__ poses, const long long* __restrict__ D, int S,
+                                                       const int32_t* __restrict__ node_scan, const double* __restrict__ node_pose, int V,
+                                                       double* __restrict__ out, int32_t* __restrict__ info)
+{
+    const int i = blockIdx.x * MP_T + threadIdx.x;
+    if (i >= S) return;
+    double o[12];
+    const int made = lpd_map_correct(poses, (const int64_t*)D, S, node_scan, node_pose, V, i, o);
+    for (int k = 0; k < 12; ++k) out[(size_t)12 * i + k] = o[k];
+    atomicAdd(info + (made ? 0 : 1), 1);
+}
+
+// (key, sums) into the caller's table: 0 lost, 1 added to a cell that was there, 2 added to a cell this call created.  keys never
+// change once set, so a key that is read is final, and a slot that reads empty is settled by the compare-and-swap.
+__device__ __forceinline__ int mp_global_insert(long long* __restrict__ keys, long long* __restrict__ acc, long long capacity, long long key,
+                                                long long sx, long long sy, long long sz, long long m)
+{
+    const u64 mask = (u64)capacity - 1;
+    u64 s = lpd_map_mix(key) & mask;
+    const int probes = lpd_map_probes(capacity);
+    for (int p = 0; p < probes; ++p, s = (s + 1) & mask) {
+        long long cur = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int created = 0;
+        if (cur == LPD_MAP_EMPTY) {
+            cur = (long long)atomicCAS((u64*)(keys + s), (u64)LPD_MAP_EMPTY, (u64)key);
+            if (cur == LPD_MAP_EMPTY) {
+                cur = key;
+                created = 1;
+            }
+        }
+        if (cur == key) {
+            u64* a = (u64*)(acc + 4 * s);
+            atomicAdd(a + 0, (u64)sx);
+            atomicAdd(a + 1, (u64)sy);
+            atomicAdd(a + 2, (u64)sz);
+            atomicAdd(a + 3, (u64)m);
+            return 1 + created;
+        }
+    }
+    return 0;
+}
+
+// n floats global -> LDS: scalar elements up to the first 16-byte boundary of the global side, 16-byte loads on the body, scalar
+// elements behind it.  Nothing outside [g, g + n) is read.
+__device__ __forceinline__ void mp_copy_in(const float* __restrict__ g, float* s, int n, int tid)
+{
+    int head = (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
+    head = head < n ? head : n;
+    const int body = (n - head) >> 2, tail0 = head + 4 * body;
+    if (tid < head) s[tid] = g[tid];
+    for (int v = tid; v < body; v += MP_T) {
+        const float4 a = *reinterpret_cast<const float4*>(g + head + 4 * v);
+        float* d = s + head + 4 * v;
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
+    }
+    if (tid < n - tail0) s[tail0 + tid] = g[tail0 + tid];
+}
+
+template <bool DIRECT>
+__global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ points, int ld, int rows, const int32_t* __restrict__ offsets,
+                                                      const double* __restrict__ poses, int scan0, int scan1, const double* __restrict__ origin,
+                                                      float inv_cell, long long* __restrict__ keys, long long* __restrict__ acc,
+                                                      long long capacity, long long* __restrict__ info)
+{
+    __shared__ float buf[3 * MP_CH];
+    __shared__ LpdDriveRel rel[MP_CAP];
+    __shared__ int32_t soff[MP_CAP + 1];
+    __shared__ int span[2];
+    __shared__ u64 cnt[4];                                    // inserted, dropped, lost, created
+    __shared__ u64 lkey[DIRECT ? 1 : MP_LS];
+    __shared__ u64 lacc[DIRECT ? 4 : 4 * MP_LS];
+    const int tid = threadIdx.x;
+    const long long lo = offsets[scan0], hi = offsets[scan1];      // 0 <= scan0 < scan1 <= S: the host's check
+    if (!(lo >= 0 && lo <= hi && hi <= rows)) return;              // uniform: nothing is read
+    const long long c0 = (long long)blockIdx.x * MP_CH;
+    const long long g0 = c0 > lo ? c0 : lo, g1 = c0 + MP_CH < hi ? c0 + MP_CH : hi;
+    if (g0 >= g1) return;                                          // uniform
+    const int cn = (int)(g1 - g0);                                 // 1 .. 1024 rows, all in [lo, hi) within [0, rows)
+    if (tid < 4) cnt[tid] = 0;
+    if (!DIRECT)
+        for (int s = tid; s < MP_LS; s += MP_T) {
+            lkey[s] = (u64)LPD_MAP_EMPTY;
+            lacc[4 * s + 0] = 0; lacc[4 * s + 1] = 0; lacc[4 * s + 2] = 0; lacc[4 * s + 3] = 0;
+        }
+    if (tid == 0) span[0] = lpd_drive_scan_of(offsets, scan0, scan1, g0);
+    if (tid == 64) span[1] = lpd_drive_scan_of(offsets, scan0, scan1, g1 - 1);
+    __syncthreads();
+    const int i_lo = span[0], i_hi = span[1];      // both in [scan0, scan1 - 1]
+    // is this part of the table one?  (lpd_map_chunk_ok, its loop shared among the threads)
+    int bad = !(i_lo <= i_hi && (long long)offsets[i_lo] <= g0 && g1 - 1 < (long long)offsets[i_hi + 1]);
+    if (!bad)
+        for (int i = i_lo + tid; i <= i_hi; i += MP_T) bad |= offsets[i] > offsets[i + 1];
+    if (__syncthreads_or(bad)) {                   // not read: its rows are counted as dropped
+        if (tid == 0) atomicAdd((u64*)info + 1, (u64)cn);
+        return;
+    }
+    const float* src = points + (size_t)g0 * ld;
+    if (ld == 3) {
+        mp_copy_in(src, buf, 3 * cn, tid);
+    } else if (ld == 4 && ((uintptr_t)points & 15) == 0) {
+#pragma unroll
+        for (int k = 0; k < MP_R; ++k) {
+            const int j = k * MP_T + tid;
+            if (j < cn) {
+                const float4 a = *reinterpret_cast<const float4*>(src + (size_t)j * 4);
+                buf[3 * j + 0] = a.x; buf[3 * j + 1] = a.y; buf[3 * j + 2] = a.z;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < MP_R; ++k) {
+            const int j = k * MP_T + tid;
+            if (j < cn) {
+                const float* p = src + (size_t)j * ld;
+                buf[3 * j + 0] = p[0]; buf[3 * j + 1] = p[1]; buf[3 * j + 2] = p[2];
+            }
+        }
+    }
+    const int ns = i_hi - i_lo + 1;
+    const bool table = ns <= MP_CAP;
+    const double org[3] = {origin[0], origin[1], origin[2]};
+    if (table) {
+        if (tid < ns) rel[tid] = lpd_map_rel(poses + (size_t)12 * (i_lo + tid), org);
+        if (tid <= ns) soff[tid] = offsets[i_lo + tid];      // i_lo + ns = i_hi + 1 <= scan1
+    }
+    __syncthreads();
+    u64 n_ins = 0, n_drop = 0, n_lost = 0, n_new = 0;
+#pragma unroll
+    for (int k = 0; k < MP_R; ++k) {
+        const int j = k * MP_T + tid;
+        if (j < cn) {
+            const float x = buf[3 * j + 0], y = buf[3 * j + 1], z = buf[3 * j + 2];
+            float w[3];
+            int64_t key, U[3];
+            int ok;
+            if (table) {
+                ok = lpd_map_row(rel[lpd_drive_scan_of(soff, 0, ns, g0 + j)], inv_cell, x, y, z, w, &key, U);
+            } else {
+                const int i = lpd_drive_scan_of(offsets, i_lo, i_hi + 1, g0 + j);
+                ok = lpd_map_row(lpd_map_rel(poses + (size_t)12 * i, org), inv_cell, x, y, z, w, &key, U);
+            }
+            if (!ok) {
+                ++n_drop;
+                continue;
+            }
+            bool placed = false;
+            if (!DIRECT) {
+                unsigned s = (unsigned)(lpd_map_mix(key) >> 32) & (MP_LS - 1);      // the high half: not the bits of the global slot
+                for (int p = 0; p < LPD_MAP_LDS_PROBES && !placed; ++p, s = (s + 1) & (MP_LS - 1)) {
+                    u64 cur = __hip_atomic_load(&lkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (cur == (u64)LPD_MAP_EMPTY) cur = atomicCAS(&lkey[s], (u64)LPD_MAP_EMPTY, (u64)key);
+                    if (cur == (u64)LPD_MAP_EMPTY || cur == (u64)key) {
+                        atomicAdd(&lacc[4 * s + 0], (u64)U[0]);
+                        atomicAdd(&lacc[4 * s + 1], (u64)U[1]);
+                        atomicAdd(&lacc[4 * s + 2], (u64)U[2]);
+                        atomicAdd(&lacc[4 * s + 3], (u64)1);
+                        placed = true;
+                    }
+                }
+            }
+            if (!placed) {
+                const int r = mp_global_insert(keys, acc, capacity, key, U[0], U[1], U[2], 1);
+                if (r) ++n_ins; else ++n_lost;
+                if (r == 2) ++n_new;
+            }
+        }
+    }
+    if (!DIRECT) {
+        __syncthreads();
+        for (int s = tid; s < MP_LS; s += MP_T) {
+            const u64 key = lkey[s];
+            if (key != (u64)LPD_MAP_EMPTY) {
+                const u64 m = lacc[4 * s + 3];
+                const int r = mp_global_insert(keys, acc, capacity, (long long)key, (long long)lacc[4 * s + 0], (long long)lacc[4 * s + 1],
+                                               (long long)lacc[4 * s + 2], (long long)m);
+                if (r) n_ins += m; else n_lost += m;
+                if (r == 2) ++n_new;
+            }
+        }
+    }
+    if (n_ins) atomicAdd(&cnt[0], n_ins);
+    if (n_drop) atomicAdd(&cnt[1], n_drop);
+    if (n_lost) atomicAdd(&cnt[2], n_lost);
+    if (n_new) atomicAdd(&cnt[3], n_new);
+    __syncthreads();
+    if (tid < 4 && cnt[tid]) atomicAdd((u64*)info + tid, cnt[tid]);
+}
+
+__global__ __launch_bounds__(MP_T) void rehash_kernel(const long long* __restrict__ keys_in, const long long* __restrict__ acc_in, long long cap_in,
+                                                      long long* __restrict__ keys, long long* __restrict__ acc, long long capacity,
+                                                      long long* __restrict__ info)
+{
+    const long long s = (long long)blockIdx.x * MP_T + threadIdx.x;
+    if (s >= cap_in) return;
+    const long long key = keys_in[s];
+    if (key < 0) return;
+    const long long m = acc_in[4 * s + 3];
+    const int r = mp_global_insert(keys, acc, capacity, key, acc_in[4 * s + 0], acc_in[4 * s + 1], acc_in[4 * s + 2], m);
+    atomicAdd((u64*)info + (r ? 0 : 2), (u64)m);
+    if (r == 2) atomicAdd((u64*)info + 3, (u64)1);
+}
+
+bool mp_capacity_ok(long long c) { return c >= LPD_MAP_MIN_CAPACITY && c <= LPD_MAP_MAX_CAPACITY && (c & (c - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int lpd_drive_correct(const double* poses, const long long* D, int S, const int32_t* node_scan, const double* node_pose, int V,
+                                 double* out, int32_t* info, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    LPD_CHECK_ARG(poses && D && node_scan && node_pose && out && info, "lpd_drive_correct: null pointer");
+    LPD_CHECK_ARG(S >= 1 && S <= LPD_DRIVE_MAX_SCANS, "lpd_drive_correct: S=%d outside 1 .. 2^22", S);
+    LPD_CHECK_ARG(V >= 1 && V <= S, "lpd_drive_correct: V=%d outside 1 .. S=%d", V, S);
+    LPD_CHECK_ARG((const void*)out != (const void*)poses && (const void*)out != (const void*)node_pose, "lpd_drive_correct: out must not alias its inputs");
+    hipLaunchKernelGGL(correct_kernel, dim3((S + MP_T - 1) / MP_T), dim3(MP_T), 0, stream, poses, D, S, node_scan, node_pose, V, out, info);
+    LPD_CHECK_LAUNCH("lpd_drive_correct");
+    return LPD_OK;
+}
+
+extern "C" int lpd_map_insert(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,
+                              const double* origin, float inv_cell, long long* keys, long long* acc, long long capacity, long long* info,
+                              void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    LPD_CHECK_ARG(points && offsets && poses && origin && keys && acc && info, "lpd_map_insert: null pointer");
+    LPD_CHECK_ARG(ld >= 3 && rows >= 1, "lpd_map_insert: bad dims ld=%d rows=%d (ld >= 3, rows >= 1)", ld, rows);
+    LPD_CHECK_ARG(S >= 1 && S <= LPD_DRIVE_MAX_SCANS, "lpd_map_insert: S=%d outside 1 .. 2^22", S);
+    LPD_CHECK_ARG(scan0 >= 0 && scan0 < scan1 && scan1 <= S, "lpd_map_insert: scans %d .. %d outside 0 .. S=%d", scan0, scan1, S);
+    LPD_CHECK_ARG(inv_cell >= LPD_MAP_INV_CELL_MIN && inv_cell <= LPD_MAP_INV_CELL_MAX,
+                  "lpd_map_insert: inv_cell=%g outside 1/16 .. 1024 (a cell of 2^-10 .. 16 m keeps every sum inside an int64)", (double)inv_cell);
+    LPD_CHECK_ARG(mp_capacity_ok(capacity), "lpd_map_insert: capacity=%lld is not a power of two in 16 .. 2^36", capacity);
+    const dim3 grid((unsigned)(((long long)rows + MP_CH - 1) / MP_CH));
+    if (lpd_debug("map-direct", 0))
+        hipLaunchKernelGGL(insert_kernel<true>, grid, dim3(MP_T), 0, stream, points, ld, rows, offsets, poses, scan0, scan1, origin, inv_cell, keys,
+                           acc, capacity, info);
+    else
+        hipLaunchKernelGGL(insert_kernel<false>, grid, dim3(MP_T), 0, stream, points, ld, rows, offsets, poses, scan0, scan1, origin, inv_cell, keys,
+                           acc, capacity, info);
+    LPD_CHECK_LAUNCH("lpd_map_insert");
+    return LPD_OK;
+}
+
+extern "C" int lpd_map_rehash(const long long* keys_in, const long long* acc_in, long long capacity_in, long long* keys, long long* acc,
+                              long long capacity, long long* info, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    LPD_CHECK_ARG(keys_in && acc_in && keys && acc && info, "lpd_map_rehash: null pointer");
+    LPD_CHECK_ARG(mp_capacity_ok(capacity_in) && mp_capacity_ok(capacity), "lpd_map_rehash: capacities %lld -> %lld are not powers of two in 16 .. 2^36",
+                  capacity_in, capacity);
+    LPD_CHECK_ARG((const void*)keys_in != (const void*)keys && (const void*)acc_in != (const void*)acc, "lpd_map_rehash: the new table must not be the old one");
+    hipLaunchKernelGGL(rehash_kernel, dim3((unsigned)((capacity_in + MP_T - 1) / MP_T)), dim3(MP_T), 0, stream, keys_in, acc_in, capacity_in, keys, acc,
+                       capacity, info);
+    LPD_CHECK_LAUNCH("lpd_map_rehash");
+    return LPD_OK;
+}

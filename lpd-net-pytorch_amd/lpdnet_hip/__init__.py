@@ -5,3 +5,4 @@ from . import verify  # noqa: F401
 from . import sequence  # noqa: F401
 from . import posegraph  # noqa: F401
 from . import consistency  # noqa: F401
+from . import mapping  # noqa: F401

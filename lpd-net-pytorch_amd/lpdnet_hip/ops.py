@@ -1539,6 +1539,130 @@ def drive_rows(points, offsets, poses, plan, out_off, max_len, out_rows, frame=1
     return out
 
 
+# the drive map (csrc/lpd_map.hip); the numbers are those of csrc/lpd_map_math.h
+MAP_CHUNK, MAP_MAX_PROBES, MAP_MIN_CAPACITY, MAP_MAX_CAPACITY, MAP_QLIM = 1024, 128, 16, 1 << 36, 1 << 20
+MAP_MIN_CELL, MAP_MAX_CELL = 2.0 ** -10, 16.0
+MAP_UNITS_PER_METRE = 65536
+
+
+def drive_correct(poses, D, node_scan, node_pose, info=None):
+    """The corrected pose of every scan from the optimised nodes (lpd_drive_correct; definition in include/lpd_hip.h): poses [S, 12]
+    float64, D [S] int64 (drive_distance), node_scan [V] int32 non-decreasing in [0, S), node_pose [V, 12] float64, all on the device
+    -> (out [S, 12] float64, info [2] int32 = scans made from the nodes, scans passed through; a given info is added to).  Nothing is
+    read back."""
+    poses, S = _drive_poses("drive_correct", poses)
+    _req(D, "D", torch.int64)
+    _req(node_scan, "node_scan", torch.int32)
+    _req(node_pose, "node_pose", torch.float64)
+    if D is None or node_scan is None or node_pose is None:
+        raise TypeError("drive_correct: D, node_scan and node_pose are tensors")
+    if tuple(D.shape) != (S,):
+        raise ValueError(f"drive_correct: D must be [S] = ({S},), got {tuple(D.shape)}")
+    if node_scan.dim() != 1 or not 1 <= node_scan.shape[0] <= S:
+        raise ValueError(f"drive_correct: node_scan must be [V] with 1 <= V <= S = {S}, got {tuple(node_scan.shape)}")
+    V = node_scan.shape[0]
+    if tuple(node_pose.shape) != (V, 12):
+        raise ValueError(f"drive_correct: node_pose must be [V, 12] = ({V}, 12), got {tuple(node_pose.shape)}")
+    if len({poses.device, D.device, node_scan.device, node_pose.device}) != 1:
+        raise ValueError("drive_correct: poses, D, node_scan and node_pose must be on one device")
+    if info is None:
+        info = _zeros((2,), torch.int32, poses.device)
+    else:
+        _req(info, "info", torch.int32)
+        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != poses.device:
+            raise ValueError(f"drive_correct: info must be a contiguous [2] int32 tensor on {poses.device}")
+    out = torch.empty((S, 12), dtype=torch.float64, device=poses.device)
+    _call("drive_correct", _lib.load().lpd_drive_correct, _ptr(poses), _ptr(D.contiguous()), S, _ptr(node_scan.contiguous()),
+          _ptr(node_pose.contiguous()), V, _ptr(out), _ptr(info), _stream())
+    return out, info
+
+
+def map_inv_cell(cell, what="map_insert"):
+    """A cell in metres -> the fp32 1.0f / cell that lpd_map_insert takes, as a Python float (cell in 2^-10 .. 16 m)"""
+    if isinstance(cell, bool) or not isinstance(cell, numbers.Real):
+        raise TypeError(f"{what}: cell must be a number of metres, got {type(cell).__name__}")
+    cell = float(cell)
+    if not MAP_MIN_CELL <= cell <= MAP_MAX_CELL:
+        raise ValueError(f"{what}: cell={cell} m outside 2^-10 .. 16 (the bound that keeps every cell's sums inside an int64)")
+    c32 = torch.tensor(cell, dtype=torch.float32)
+    inv = float(torch.tensor(1.0, dtype=torch.float32) / c32)
+    if not 1.0 / MAP_MAX_CELL <= inv <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: cell={cell} m outside 2^-10 .. 16")
+    return inv
+
+
+def _map_table(what, keys, acc, info):
+    _req(keys, "keys", torch.int64)
+    _req(acc, "acc", torch.int64)
+    _req(info, "info", torch.int64)
+    if keys is None or acc is None or info is None:
+        raise TypeError(f"{what}: keys, acc and info are tensors")
+    cap = keys.shape[0] if keys.dim() == 1 else 0
+    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
+    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous():
+        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor, got {tuple(acc.shape)}")
+    if tuple(info.shape) != (4,) or not info.is_contiguous():
+        raise ValueError(f"{what}: info must be a contiguous [4] tensor, got {tuple(info.shape)}")
+    if not (keys.device == acc.device == info.device):
+        raise ValueError(f"{what}: keys, acc and info must be on one device")
+    return cap
+
+
+def map_table(capacity, device):
+    """An empty table for map_insert -> (keys [capacity] int64 = -1, acc [capacity, 4] int64 = 0, info [4] int64 = 0)"""
+    capacity = int(capacity)
+    if not MAP_MIN_CAPACITY <= capacity <= MAP_MAX_CAPACITY or capacity & (capacity - 1):
+        raise ValueError(f"map_table: capacity={capacity} is not a power of two in 16 .. 2^36")
+    return (torch.full((capacity,), -1, dtype=torch.int64, device=device), torch.zeros((capacity, 4), dtype=torch.int64, device=device),
+            torch.zeros((4,), dtype=torch.int64, device=device))
+
+
+def map_insert(points, offsets, poses, origin, inv_cell, keys, acc, info, scan0=0, scan1=None):
+    """The scans scan0 .. scan1-1 of posed scans into a voxel hash table (lpd_map_insert; definition in include/lpd_hip.h): points
+    [rows, >=3] fp32 with contiguous rows, offsets [S+1] int32, poses [S, 12] float64 and origin [3] float64 on the device; inv_cell =
+    map_inv_cell(cell); keys / acc / info the caller's table (map_table), added to.  Nothing is read back: whether rows were lost is
+    in info[2]."""
+    what = "map_insert"
+    _req(points, "points")
+    _req(origin, "origin", torch.float64)
+    poses, S = _drive_poses(what, poses)
+    if points is None or origin is None:
+        raise TypeError(f"{what}: points and origin are tensors")
+    ld = _rows(points, "points")
+    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    offsets = _drive_offsets(what, offsets, S)
+    if tuple(origin.shape) != (3,):
+        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
+    cap = _map_table(what, keys, acc, info)
+    if len({points.device, offsets.device, poses.device, origin.device, keys.device}) != 1:
+        raise ValueError(f"{what}: points, offsets, poses, origin and the table must be on one device")
+    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
+    if not 0 <= scan0 < scan1 <= S:
+        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
+    inv_cell = float(inv_cell)
+    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    _call("map_insert", _lib.load().lpd_map_insert, _ptr(points), ld, points.shape[0], _ptr(offsets), _ptr(poses), S, scan0, scan1,
+          _ptr(origin.contiguous()), inv_cell, _ptr(keys), _ptr(acc), cap, _ptr(info), _stream())
+
+
+def map_rehash(keys_in, acc_in, keys, acc, info):
+    """Every occupied slot of one table into another (lpd_map_rehash): how a table grows.  info [4] int64 of the new table is added to
+    (rows = the cells' counts, cells created)."""
+    what = "map_rehash"
+    _req(keys_in, "keys_in", torch.int64)
+    _req(acc_in, "acc_in", torch.int64)
+    cap = _map_table(what, keys, acc, info)
+    cap_in = _map_table(what, keys_in, acc_in, info)
+    if keys_in.device != keys.device:
+        raise ValueError(f"{what}: both tables must be on one device")
+    if keys_in.data_ptr() == keys.data_ptr() or acc_in.data_ptr() == acc.data_ptr():
+        raise ValueError(f"{what}: the new table must not be the old one")
+    _call("map_rehash", _lib.load().lpd_map_rehash, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(keys), _ptr(acc), cap, _ptr(info), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # geometric verification of retrieved places (csrc/lpd_align.hip)
 # ------------------------------------------------------------------------------------------------
