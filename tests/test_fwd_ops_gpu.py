@@ -27,16 +27,12 @@ import pytest
 import torch
 
 import launch_sizes as ls
+from fp64_checks import (ELEM_X, LEAKY, NONE, RELU, SIGMOID, SLOPE, SUM_X, U23, X3_TERM,      # noqa: F401  (the shared measure)
+                         _act, _act_scale, _check, _scaled, _seqsum)
 
 pytestmark = pytest.mark.gpu
 
-U23 = 2.0 ** -23
-ELEM_X = 4.0
-SUM_X = 2.0
-X3_TERM = 3 * 2.0 ** -18       # split-bf16 three-product form: |a b - (ah bh + ah bl + al bh)| <= (2^-18 + 2 * 2^-18) |a b|
 FLT_MIN = 1.1754943508222875e-38
-NONE, RELU, LEAKY, SIGMOID = 0, 1, 2, 3
-SLOPE = 0.01
 
 
 def _ops():
@@ -56,51 +52,6 @@ def _free():
 
 def _gen(seed):
     return torch.Generator().manual_seed(seed)
-
-
-def _scaled(got, ref, scale, exact_zero=True):
-    """max |got - ref| / scale; an element whose scale is 0 (no non-zero term) must be exact"""
-    d = (got.detach().double().cpu() - ref).abs()
-    s = scale.double()
-    if exact_zero:
-        assert bool((d[s == 0] == 0).all()), "an element without any non-zero term is not exactly 0"
-    return (d / s.clamp_min(1e-300))[s > 0].max().item() if bool((s > 0).any()) else 0.0
-
-
-def _check(tag, got, ref, f32, scale, factor):
-    """GPU error and fp32 floor of one output, both scaled by `scale`; asserts err <= factor * max(floor, 2^-23)"""
-    floor = max(_scaled(f32, ref, scale, exact_zero=False), U23)
-    err = _scaled(got, ref, scale)
-    print(f"MEASURE {tag} err={err:.3e} floor={floor:.3e} bound={factor * floor:.3e}")
-    assert err <= factor * floor, (tag, err, floor)
-    return err, floor
-
-
-def _act(pre, act):
-    if act == SIGMOID:
-        return torch.sigmoid(pre)
-    ns = {NONE: 1.0, RELU: 0.0, LEAKY: SLOPE}[act]
-    return torch.where(pre > 0, pre, pre * ns)
-
-
-def _act_scale(pre, terms, act):
-    """sum |term| of act(pre) where pre carries `terms` = sum |term|: the slope of the activation times the terms of its argument, plus
-    the value itself for the sigmoid; within 2^-20 `terms` of the kink the full scale (either side is a correct rounding)"""
-    if act == SIGMOID:
-        y = torch.sigmoid(pre)
-        return y + y * (1 - y) * terms
-    ns = {NONE: 1.0, RELU: 0.0, LEAKY: SLOPE}[act]
-    fac = torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, ns))
-    return torch.where(pre.abs() <= 2.0 ** -20 * terms, terms, terms * fac)
-
-
-def _seqsum(t, dim):
-    """float32 sum along `dim` in sequence, term after term (a loop: torch.cumsum on the CPU accumulates float32 in double)"""
-    t = t.float().movedim(dim, 0)
-    acc = torch.zeros_like(t[0])
-    for i in range(t.shape[0]):
-        acc = acc + t[i]
-    return acc
 
 
 # ================================================================== bit-exact ops

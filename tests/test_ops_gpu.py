@@ -5,7 +5,10 @@ the same formula in the norm-relative measure `_rel` = max |a - b| / max |b| ove
 is 1e-4).  That measure cannot see one wrong row or one wrong small element of a softmax or a VLAD descriptor, so the head tests below
 carry an element-wise check (`_elem`) beside it, and the modules that run the kernels at their launch sizes measure every element
 against its own scale: tests/test_launch_sizes_gpu.py, tests/test_train_bwd_ops_gpu.py and tests/test_fwd_ops_gpu.py scale each error by
-the fp64 sum |term| of that element and bound it by a float32 evaluation of the same formula.
+the fp64 sum |term| of that element and bound it by a float32 evaluation of the same formula.  The GEMM family (csrc/lpd_gemm.hip,
+csrc/lpd_gemm_t.hip, csrc/lpd_gemm_p8.hip) has that measure in tests/test_gemm_routes_gpu.py: every route of the dispatch at its smallest
+shape, on inputs with graded row and column scales, each case asserting the ops.PROFILE label of the route it names; the GEMM tests
+below keep the norm-relative gate at larger shapes.
 """
 import os
 
@@ -336,13 +339,25 @@ def test_gemm_splitk_and_batched(cuda, exact):
     A = torch.randn(6, 8192, generator=g)
     W = torch.randn(8192, 256, generator=g) / 90
     sc, sh = torch.randn(256, generator=g), torch.randn(256, generator=g)
-    out = ops.gemm(A.to(cuda), W.to(cuda), b_kmajor=True, scale=sc.to(cuda), shift=sh.to(cuda), splits=16, exact=exact)
+    prof = ops.PROFILE = {}
+    try:
+        out = ops.gemm(A.to(cuda), W.to(cuda), b_kmajor=True, scale=sc.to(cuda), shift=sh.to(cuda), splits=16, exact=exact)
+    finally:
+        ops.PROFILE = None
+    # 6 rows are below the wrapper's floor for the split form (M >= 128 and N >= 128): BOTH ids run split-K on the f32-input kernel here;
+    # split-K on the split-bf16 kernel is tests/test_gemm_routes_gpu.py (x3/nt_K192_splits3 and its neighbours)
+    assert list(prof) == ["gemm[6x256x8192]"], list(prof)
     ref = (A.double() @ W.double()) * sc.double() + sh.double()
     assert _rel(out, ref) < tol
     # batched, A stored k-major (NetVLAD aggregation shape): [b][n][f]^T @ [b][n][c]
     X = torch.randn(3, 512, 256, generator=g)
     Act = torch.rand(3, 512, 64, generator=g)
-    out = ops.gemm(X.to(cuda), Act.to(cuda), a_kmajor=True, b_kmajor=True, exact=exact)
+    prof = ops.PROFILE = {}
+    try:
+        out = ops.gemm(X.to(cuda), Act.to(cuda), a_kmajor=True, b_kmajor=True, exact=exact)
+    finally:
+        ops.PROFILE = None
+    assert list(prof) == ["gemm[256x64x512]" if exact else "gemmx3[256x64x512]"], list(prof)
     ref = torch.matmul(X.double().transpose(1, 2), Act.double())
     assert out.shape == (3, 256, 64)
     assert _rel(out, ref) < tol
