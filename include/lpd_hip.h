@@ -61,7 +61,9 @@ extern "C" {
 
 int lpd_version(void);
 const char* lpd_last_error(void);
-/* size of the `stat_ws` workspace (see Conventions): 32 replicas x 2 x 1024 doubles = 512 KiB */
+/* size of the `stat_ws` workspace (see Conventions): 32 replicas x 2 x LPD_STAT_CMAX doubles = 512 KiB; a layer of more columns is
+ * refused by the entry points that take it */
+#define LPD_STAT_CMAX 1024
 long long lpd_stat_ws_bytes(void);
 
 /*
@@ -398,6 +400,7 @@ int lpd_retrieval_topk(const float* S, const float* Q, int ldq, const float* D, 
  *   n_onepct [npairs] (one-percent hits) -- overwritten.  ws: q_rows + d_rows floats (the squared norms).  The caller guarantees that the
  *   offsets, pairs and truth_off index inside the tables (lpdnet_hip/ops.py recall_pairs checks them on the host).
  */
+#define LPD_RECALL_KMAX 64
 int lpd_recall_pairs(const float* Q, int ldq, const float* D, int ldd, int dim, const int32_t* q_off, const int32_t* d_off, int rd,
                      int q_rows, int d_rows, const int32_t* pairs, const int32_t* out_off, int npairs, int max_qtiles,
                      const int32_t* truth_off, const int32_t* truth_idx, int k, int32_t* first, uint8_t* one_pct, float* top1_sim,
@@ -486,6 +489,9 @@ int lpd_local_features(const float* xyz, int ldx, const int32_t* idx, int B, int
  * The result does not depend on thread order; rows 0 .. M-1, info and counts do not depend on the order of the raw points either
  * (the fill rows do, by definition).  No float atomics.  One 1024-thread workgroup per cloud; N > 4096: LPD_ERR_UNSUPPORTED.
  */
+#define LPD_SUBMAP_MIN_N 128           /* rung 127 has at most 125 cells, so the search cannot fail for N >= 128 */
+#define LPD_SUBMAP_MAX_N 4096
+#define LPD_SUBMAP_MAX_POINTS 1048576  /* raw points per cloud: 2^20 points x 2^20 quantisation steps stay far inside 64 bits */
 int lpd_make_submaps(const float* points, int ld, const int32_t* offsets, int B, int N, int normalize, float* out, int32_t* info,
                      float* xform, int32_t* counts, void* stream);
 
@@ -516,6 +522,10 @@ int lpd_make_submaps(const float* points, int ld, const int32_t* offsets, int B,
  *   Without rot and with sigma = 0 the output rows are bit-copies of the table rows.  An item outside [0, T) gives a cloud of zeros
  *   (no jitter either) and is never read.  N % 4 == 0 with 16-byte aligned table / out: 16-byte accesses, one point per thread else.
  */
+#define LPD_TUPLE_MAX_ITEMS 262144     /* T: the membership bitmap (32 KiB) and its scanned popcounts (32 KiB) live in LDS */
+#define LPD_TUPLE_MAX_SAMPLES 4096     /* m */
+#define LPD_TUPLE_MAX_LISTS 64         /* L and X */
+#define LPD_TUPLE_MAX_ROWS 65535       /* R, and B of lpd_gather_tuples (one grid dimension) */
 int lpd_sample_items(const int32_t* off, const int32_t* idx, int n_lists, int nnz, int T, const int32_t* lists, int L, const int32_t* extra,
                      int X, int R, int invert, int m, unsigned long long seed, int32_t* out, int32_t* count, void* stream);
 int lpd_gather_tuples(const float* table, int T, int N, const int32_t* items, int B, const float* rot, float sigma, float clip,
@@ -546,6 +556,9 @@ int lpd_gather_tuples(const float* table, int T, int N, const int32_t* items, in
  * ascending order, __ballot and a popcount of the lanes below), not from a sort.  No atomics: the same bits in every launch.
  * Limits: 1 <= S <= 4096, 0 <= Q, D <= 2^22, Q * S < 2^31.  Q == 0 launches nothing.
  */
+#define LPD_PLACES_MAX_ITEMS 4194304   /* Q and D: 2^22 */
+#define LPD_PLACES_MAX_SEGMENTS 4096   /* S (one grid dimension) */
+#define LPD_PLACES_CHUNK 1024          /* candidate positions staged in LDS at a time (16 KiB) */
 int lpd_radius_count(const double* qpos, int Q, const double* dpos, int D, const int32_t* seg_off, int S, double r, const int32_t* skip_seg,
                      const int32_t* self_item, int32_t* counts, void* stream);
 int lpd_radius_fill(const double* qpos, int Q, const double* dpos, int D, const int32_t* seg_off, int S, double r, const int32_t* skip_seg,
@@ -590,7 +603,8 @@ int lpd_radius_fill(const double* qpos, int Q, const double* dpos, int D, const 
  * is not that scan -- is dropped, not written.  plane and info NULL (both): crop only.  Both calls run one kernel on the same
  * predicate.  Integer atomics only, no float atomics: the same bits in every launch.  1 <= B <= 65535.
  */
-#define LPD_CLEAN_CHUNK 1024
+#define LPD_CLEAN_CHUNK 1024           /* rows of one workgroup */
+#define LPD_CLEAN_MAX_H 1024           /* hypotheses per scan */
 typedef struct LpdCleanParams {
     float r_min, r_max, z_lo, z_hi, seed_z_lo, seed_z_hi, tau, min_det, max_slope, clearance;
     int32_t H, min_inliers, refine;
@@ -642,6 +656,10 @@ int lpd_clean_fill(const float* points, int ld, int rows, const int32_t* offsets
  * the poses, [0, S] of the offsets and [0, rows) of the points is ever read, whatever the tables hold; no row is used as an address.
  * No atomics: the same bits in every launch.  Limits: 1 <= S <= 2^22, 1 <= W <= 65535 per call, fewer than 2^31 output rows.
  */
+#define LPD_DRIVE_MAX_SCANS 4194304        /* S: 2^22 */
+#define LPD_DRIVE_MAX_WINDOWS 65535        /* W of one call */
+#define LPD_DRIVE_MAX_WINDOW_NO 4194304    /* w0 + W: with L, T <= 2^40 and D <= 2^22 * 2^36 every sum of the plan stays under 2^63 */
+#define LPD_DRIVE_MAX_UNITS 1099511627776  /* L and T, in units of 2^-16 m: 2^40 */
 int lpd_drive_steps(const double* poses, int S, long long* q, void* stream);
 int lpd_drive_plan(const long long* D, int S, const int32_t* offsets, const double* poses, long long L, long long T, long long w0, int W,
                    int32_t* plan, double* position, void* stream);
@@ -683,6 +701,13 @@ int lpd_drive_rows(const float* points, int ld, int rows, const int32_t* offsets
  * candidate number) keys are combined by an integer maximum in a fixed order.  No float atomics; integer LDS atomics only: the same
  * bits in every launch and in any thread order.
  */
+#define LPD_ALIGN_GRID 128             /* cells per side; a row of the bitmap is 128 bits = four 32-bit words, bit ix in word ix >> 5 */
+#define LPD_ALIGN_MAX_LAYERS 4
+#define LPD_ALIGN_MAX_S 16             /* |dy|, |dx| <= S <= 16: a shift never crosses a whole word */
+#define LPD_ALIGN_MAX_H 1024           /* hypotheses per pair */
+#define LPD_ALIGN_MAX_R 8192           /* entries of the (cos, sin) table */
+#define LPD_ALIGN_MAX_POINTS 16384     /* points per cloud: a score and a cell count fit 15 bits */
+#define LPD_ALIGN_MAX_PAIRS 1048576
 long long lpd_align_workspace_bytes(int P, int H);
 int lpd_align_pairs(const float* A, int TA, const float* scaleA, const float* B, int TB, const float* scaleB, int N,
                     const int32_t* pairs, int P, const float* rot, int R, const int32_t* first, int H, const float* t0,
@@ -731,6 +756,11 @@ int lpd_align_pairs(const float* A, int TA, const float* scaleA, const float* B,
  * dims), 16-byte aligned, the caller's, one per call in flight, no state between calls.  Integer atomics only: the same bits in every
  * launch.  Every call only enqueues.
  */
+#define LPD_ICP_MAX_POINTS 16384       /* points per cloud: 2^14 terms of at most 2^40 in a sum */
+#define LPD_ICP_MAX_PAIRS 1048576
+#define LPD_ICP_MAX_ITERS 64
+#define LPD_ICP_MIN_INLIERS 6          /* the least min_inliers: six unknowns */
+#define LPD_ICP_SUMS 32                /* int64 entries of a (pass, pair): 29 used, 29..31 are 0 */
 long long lpd_icp_workspace_bytes(int P, int N, int iters);
 int lpd_point_normals(const float* xyz, int ldx, const int32_t* idx, int B, int N, int K, float* normals, float* flatness, void* stream);
 int lpd_icp_pairs(const float* A, int TA, const float* scaleA, const float* B, int TB, const float* scaleB, const float* normalsB, int N,
@@ -958,6 +988,11 @@ int lpd_loop_select(const uint64_t* adj, int ldw, const int32_t* degree, const i
  * lpd_map_rehash inserts every occupied slot of a table (keys_in, acc_in, capacity_in) into another one by rule 4, sums and counts as
  * they are: how a table grows.  info as above (rows inserted = the cells' counts m, cells created).
  */
+#define LPD_MAP_CHUNK 1024                 /* input rows of one workgroup: chunk c is the rows 1024 c .. 1024 c + 1023 of the table */
+#define LPD_MAP_MAX_PROBES 128             /* probes in the caller's table before a row is lost (never more than its capacity) */
+#define LPD_MAP_MIN_CAPACITY 16
+#define LPD_MAP_MAX_CAPACITY 68719476736   /* 2^36 */
+#define LPD_MAP_QLIM 1048576               /* 2^20: a cell index lies in [-2^20, 2^20) */
 int lpd_drive_correct(const double* poses, const long long* D, int S, const int32_t* node_scan, const double* node_pose, int V, double* out,
                       int32_t* info, void* stream);
 int lpd_map_insert(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,

@@ -11,20 +11,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_ALIGN_FN __host__ __device__ __forceinline__
 #else
 #define LPD_ALIGN_FN static inline
 #endif
 
-#define LPD_ALIGN_GRID 128                // cells per side; a row of the bitmap is 128 bits = four 32-bit words, bit ix in word ix >> 5
-#define LPD_ALIGN_HALF 64.0f              // the cell of the origin
-#define LPD_ALIGN_MAX_LAYERS 4
-#define LPD_ALIGN_MAX_S 16                // |dy|, |dx| <= S <= 16: a shift never crosses a whole word
-#define LPD_ALIGN_MAX_H 1024              // hypotheses per pair
-#define LPD_ALIGN_MAX_R 8192              // entries of the (cos, sin) table
-#define LPD_ALIGN_MAX_POINTS 16384        // points per cloud: a score and a cell count fit 15 bits
-#define LPD_ALIGN_MAX_PAIRS (1 << 20)
+// LPD_ALIGN_GRID and the LPD_ALIGN_MAX_* (LAYERS, S, H, R, POINTS, PAIRS) are the public header's
+#define LPD_ALIGN_HALF 64.0f              // the cell of the origin: LPD_ALIGN_GRID / 2
 #define LPD_ALIGN_SPAN 33                 // 2 * LPD_ALIGN_MAX_S + 1: the radix of (dy + S, dx + S) in the candidate's number
 
 LPD_ALIGN_FN bool lpd_align_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }      // false for NaN and +-inf

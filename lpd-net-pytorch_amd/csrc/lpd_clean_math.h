@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
 #include "lpd_tuple_math.h"      // lpd_philox4x32_10: the draws of the hypotheses
 
 #if defined(__HIPCC__)
@@ -19,10 +20,9 @@
 #define LPD_CLEAN_FN static inline
 #endif
 
-#define LPD_CLEAN_MAX_H 1024              // hypotheses per scan
+// LPD_CLEAN_MAX_H and LPD_CLEAN_CHUNK (256 threads x LPD_CLEAN_LANE_ROWS) are the public header's
 #define LPD_CLEAN_MAX_RANGE 512.0f        // r_max, metres: |dx| <= 1024 m, so |X| <= 2^20 and 2^20 rows x 2^40 < 2^63
 #define LPD_CLEAN_MAX_POINTS (1 << 20)    // rows of one scan (LPD_SUBMAP_MAX_POINTS)
-#define LPD_CLEAN_CHUNK 1024              // rows of one workgroup: 256 threads x LPD_CLEAN_LANE_ROWS
 #define LPD_CLEAN_LANE_ROWS 4
 #define LPD_CLEAN_QSCALE 1024.0f          // quantisation steps per metre (2^-10 m, a little under 1 mm)
 #define LPD_CLEAN_QMAX 1048576.0f         // the quantised coordinate is clamped to +-2^20 before the conversion to an integer

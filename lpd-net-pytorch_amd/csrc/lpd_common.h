@@ -71,8 +71,7 @@ __device__ __forceinline__ float lpd_act_any(float v, int act, float slope)
 // atomics on ONE address behind a __threadfence took 620 us.)  The replicas live in a CALLER-OWNED workspace (the `stat_ws` argument of every entry point
 // that reduces over blocks: lpd_stat_ws_bytes() bytes, zero-filled once by the caller, left all-zero by every call that returns
 // LPD_OK; one workspace per stream -- launches on one stream are ordered, so they share it).  The library allocates nothing.
-#define LPD_STAT_REPLICAS 32
-#define LPD_STAT_CMAX 1024
+#define LPD_STAT_REPLICAS 32      // (the columns, LPD_STAT_CMAX, are the public header's)
 struct LpdStatWs {
     double* rep;             // [LPD_STAT_REPLICAS][2][LPD_STAT_CMAX], all zero between (statistics kernel, lpd_stat_finish) pairs
     double* sum() const { return rep; }                      // what the kernels take in place of the caller's sum / sumsq pointers

@@ -13,13 +13,15 @@
 //           per row.  The relative poses of the chunk's scans are computed ONCE per workgroup in float64 by the first threads and kept
 //           in LDS as fp32 (DR_CAP = 64 scans: a pushbroom chunk holds two or three, a sweep chunk one); each row finds its scan by a
 //           binary search in the LDS copy of the chunk's offsets.  A chunk of more than DR_CAP scans (scans of a handful of rows)
-//           lets every row compute its own relative pose with the same function: the same bits, by the slow road.
+//           lets every row compute its own relative pose with the same function: the same bits, by the slow road.  The copies, the
+//           load, the search for the chunk's scans and the pose table are lpd_scan_chunk.h, shared with lpd_map_insert.
 // No atomics.  Every index that becomes an address is checked against its table first: plan, out_off and offsets are the caller's
 // device memory and may hold anything.
 #include <math.h>
 
 #include "lpd_common.h"
 #include "lpd_drive_math.h"
+#include "lpd_scan_chunk.h"
 
 namespace {
 
@@ -27,6 +29,7 @@ constexpr int DR_T = 256;
 constexpr int DR_CH = LPD_DRIVE_CHUNK;
 constexpr int DR_R = DR_CH / DR_T;      // rows per thread
 constexpr int DR_CAP = 64;              // relative poses a workgroup keeps in LDS
+using Chunk = LpdScanChunk<DR_T, DR_CH, DR_CAP>;
 
 __global__ __launch_bounds__(DR_T) void steps_kernel(const double* __restrict__ poses, int S, long long* __restrict__ q)
 {
@@ -54,37 +57,6 @@ __global__ __launch_bounds__(DR_T) void plan_kernel(const long long* __restrict_
     position[3 * j + 2] = win.ref >= 0 ? t[11] : 0.0;
 }
 
-// n floats global -> LDS (copy_in) or LDS -> global (copy_out): scalar elements up to the first 16-byte boundary of the GLOBAL side,
-// 16-byte accesses on the body, scalar elements behind it.  Nothing outside [g, g + n) is touched.
-__device__ __forceinline__ int dr_head(const float* g, int n)
-{
-    const int h = (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
-    return h < n ? h : n;
-}
-
-__device__ __forceinline__ void dr_copy_in(const float* __restrict__ g, float* s, int n, int tid)
-{
-    const int head = dr_head(g, n), body = (n - head) >> 2, tail0 = head + 4 * body;
-    if (tid < head) s[tid] = g[tid];
-    for (int v = tid; v < body; v += DR_T) {
-        const float4 a = *reinterpret_cast<const float4*>(g + head + 4 * v);
-        float* d = s + head + 4 * v;
-        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
-    }
-    if (tid < n - tail0) s[tail0 + tid] = g[tail0 + tid];
-}
-
-__device__ __forceinline__ void dr_copy_out(float* __restrict__ g, const float* s, int n, int tid)
-{
-    const int head = dr_head(g, n), body = (n - head) >> 2, tail0 = head + 4 * body;
-    if (tid < head) g[tid] = s[tid];
-    for (int v = tid; v < body; v += DR_T) {
-        const float* d = s + head + 4 * v;
-        *reinterpret_cast<float4*>(g + head + 4 * v) = make_float4(d[0], d[1], d[2], d[3]);
-    }
-    if (tid < n - tail0) g[tail0 + tid] = s[tail0 + tid];
-}
-
 __global__ __launch_bounds__(DR_T) void rows_kernel(const float* __restrict__ points, int ld, int rows, const int32_t* __restrict__ offsets,
                                                     const double* __restrict__ poses, int S, const int32_t* __restrict__ plan,
                                                     const int32_t* __restrict__ out_off, int frame, int max_len, float* __restrict__ out)
@@ -101,64 +73,28 @@ __global__ __launch_bounds__(DR_T) void rows_kernel(const float* __restrict__ po
     if (!(in0 >= 0 && in1 - in0 == n && in1 <= rows && ob >= 0 && oe - ob == n)) return;
     const int cn = n - c0 < DR_CH ? n - c0 : DR_CH;      // rows of this chunk
     const long long g0 = in0 + c0;                       // its first input row; g0 + cn <= in1 <= rows
-    const float* src = points + (size_t)g0 * ld;
-    if (ld == 3) {
-        dr_copy_in(src, buf, 3 * cn, tid);
-    } else if (ld == 4 && ((uintptr_t)points & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k < DR_R; ++k) {
-            const int j = k * DR_T + tid;
-            if (j < cn) {
-                const float4 a = *reinterpret_cast<const float4*>(src + (size_t)j * 4);
-                buf[3 * j + 0] = a.x; buf[3 * j + 1] = a.y; buf[3 * j + 2] = a.z;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < DR_R; ++k) {
-            const int j = k * DR_T + tid;
-            if (j < cn) {
-                const float* p = src + (size_t)j * ld;
-                buf[3 * j + 0] = p[0]; buf[3 * j + 1] = p[1]; buf[3 * j + 2] = p[2];
-            }
-        }
-    }
-    // the scans of the chunk's first and last row: two waves, one search each
-    if (tid == 0) span[0] = lpd_drive_scan_of(offsets, first, end, g0);
-    if (tid == 64) span[1] = lpd_drive_scan_of(offsets, first, end, g0 + cn - 1);
+    Chunk::load(points, ld, g0, cn, buf, tid);
+    Chunk::find_span(offsets, first, end, g0, cn, span, tid);
     __syncthreads();
     const int i_lo = span[0], i_hi = span[1] >= span[0] ? span[1] : span[0];      // first <= i_lo <= i_hi < end
     const int ns = i_hi - i_lo + 1;
-    const bool table = ns <= DR_CAP;
     const double* Pr = poses + (size_t)12 * ref;
-    if (table) {
-        if (tid < ns) rel[tid] = lpd_drive_rel(poses + (size_t)12 * (i_lo + tid), Pr, frame);
-        if (tid <= ns) soff[tid] = offsets[i_lo + tid];      // i_lo + ns = i_hi + 1 <= end <= S
-        __syncthreads();
-    }
+    const auto pose = [&](int i) { return lpd_drive_rel(poses + (size_t)12 * i, Pr, frame); };
+    const bool table = Chunk::poses(offsets, i_lo, ns, rel, soff, tid, pose);      // i_lo + ns = i_hi + 1 <= end <= S
+    if (table) __syncthreads();
 #pragma unroll
     for (int k = 0; k < DR_R; ++k) {
         const int j = k * DR_T + tid;
         if (j < cn) {
             const float x = buf[3 * j + 0], y = buf[3 * j + 1], z = buf[3 * j + 2];
-            float o0, o1, o2;
-            if (table) {
-                const LpdDriveRel& r = rel[lpd_drive_scan_of(soff, 0, ns, g0 + j)];
-                o0 = lpd_drive_coord(r.m + 0, r.u[0], x, y, z);
-                o1 = lpd_drive_coord(r.m + 3, r.u[1], x, y, z);
-                o2 = lpd_drive_coord(r.m + 6, r.u[2], x, y, z);
-            } else {
-                const int i = lpd_drive_scan_of(offsets, i_lo, i_hi + 1, g0 + j);
-                const LpdDriveRel r = lpd_drive_rel(poses + (size_t)12 * i, Pr, frame);
-                o0 = lpd_drive_coord(r.m + 0, r.u[0], x, y, z);
-                o1 = lpd_drive_coord(r.m + 3, r.u[1], x, y, z);
-                o2 = lpd_drive_coord(r.m + 6, r.u[2], x, y, z);
-            }
-            buf[3 * j + 0] = o0; buf[3 * j + 1] = o1; buf[3 * j + 2] = o2;      // the row's own three floats: no other thread reads them
+            const LpdDriveRel r = Chunk::row_pose(table, rel, soff, offsets, i_lo, ns, g0 + j, pose);
+            buf[3 * j + 0] = lpd_drive_coord(r.m + 0, r.u[0], x, y, z);      // the row's own three floats: no other thread reads them
+            buf[3 * j + 1] = lpd_drive_coord(r.m + 3, r.u[1], x, y, z);
+            buf[3 * j + 2] = lpd_drive_coord(r.m + 6, r.u[2], x, y, z);
         }
     }
     __syncthreads();
-    dr_copy_out(out + (size_t)(ob + c0) * 3, buf, 3 * cn, tid);
+    Chunk::copy_out(out + (size_t)(ob + c0) * 3, buf, 3 * cn, tid);
 }
 
 }  // namespace

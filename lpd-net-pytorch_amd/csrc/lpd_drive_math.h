@@ -12,16 +12,15 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_DRIVE_FN __host__ __device__ __forceinline__
 #else
 #define LPD_DRIVE_FN static inline
 #endif
 
-#define LPD_DRIVE_MAX_SCANS (1 << 22)        // S
-#define LPD_DRIVE_MAX_WINDOWS 65535          // W of one call
-#define LPD_DRIVE_MAX_WINDOW_NO (1 << 22)    // w0 + W: with L, T <= 2^40 and D <= 2^22 * 2^36 every sum below stays under 2^63
-#define LPD_DRIVE_MAX_UNITS (1LL << 40)      // L and T, in units of 2^-16 m
+// LPD_DRIVE_MAX_SCANS, LPD_DRIVE_MAX_WINDOWS, LPD_DRIVE_MAX_WINDOW_NO and LPD_DRIVE_MAX_UNITS are the public header's
 #define LPD_DRIVE_MAX_POINTS (1 << 20)       // rows of one window (LPD_SUBMAP_MAX_POINTS)
 #define LPD_DRIVE_CHUNK 1024                 // rows of one workgroup
 #define LPD_DRIVE_QSCALE 65536.0             // distance units per metre

@@ -14,6 +14,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #include "lpd_feat_math.h"
 
 #if defined(__HIPCC__)
@@ -22,15 +24,11 @@
 #define LPD_ICP_FN static inline
 #endif
 
-#define LPD_ICP_MAX_POINTS 16384          // points per cloud: 2^14 terms of at most 2^40 in a sum
-#define LPD_ICP_MAX_PAIRS (1 << 20)
-#define LPD_ICP_MAX_ITERS 64
-#define LPD_ICP_MIN_INLIERS 6             // the least min_inliers: six unknowns
+// LPD_ICP_MAX_POINTS, LPD_ICP_MAX_PAIRS, LPD_ICP_MAX_ITERS, LPD_ICP_MIN_INLIERS and LPD_ICP_SUMS are the public header's
 #define LPD_ICP_MAX_DMAX 16.0f            // metres
 #define LPD_ICP_RANGE 512.0f              // a transformed point beyond +-512 m on any axis has no correspondence
 #define LPD_ICP_Q 1024.0f                 // quantisation steps per unit of J and r
 #define LPD_ICP_CLAMP 1048576.0f          // 2^20: |Ji|, |ri| <= 2^20, a product <= 2^40
-#define LPD_ICP_SUMS 32                   // int64 entries of a (pass, pair): 29 used, 29..31 are 0
 #define LPD_ICP_SUM_M 0                   // the count
 #define LPD_ICP_SUM_H 1                   // 21 entries sum Ji_a Ji_b, a <= b, row-major over the upper triangle
 #define LPD_ICP_SUM_G 22                  // 6 entries sum Ji_a ri

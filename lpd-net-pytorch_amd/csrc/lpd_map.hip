@@ -3,8 +3,8 @@
 //
 //   correct  one thread per scan: a binary search over node_scan, two rigid candidates in float64, their blend.  The only atomics are
 //            the two counters (the compiler folds a wave's adds into one).
-//   insert   grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, MP_T = 256 threads.  A chunk is loaded as lpd_drive_rows loads it
-//            (ld == 3: a flat copy with 16-byte accesses on the aligned body; ld == 4 with an aligned table: one 16-byte load a row), the
+//   insert   grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, MP_T = 256 threads.  A chunk is loaded as lpd_drive_rows loads it,
+//            by the same code (lpd_scan_chunk.h; ld == 3: a flat copy with 16-byte accesses on the aligned body; ld == 4 with an aligned table: one 16-byte load a row), the
 //            fp32 poses of its scans are made once per workgroup in float64 (MP_CAP = 64 of them; a chunk of more scans lets every row
 //            make its own, the same bits), and every row becomes (key, Ux, Uy, Uz).
 //              aggregated form (the default): the rows of the chunk are summed in a table of LPD_MAP_LDS_SLOTS slots in LDS first --
@@ -21,6 +21,7 @@
 
 #include "lpd_common.h"
 #include "lpd_map_math.h"
+#include "lpd_scan_chunk.h"
 
 namespace {
 
@@ -29,6 +30,7 @@ constexpr int MP_CH = LPD_MAP_CHUNK;
 constexpr int MP_R = MP_CH / MP_T;      // rows per thread
 constexpr int MP_CAP = 64;              // poses a workgroup keeps in LDS
 constexpr int MP_LS = LPD_MAP_LDS_SLOTS;
+using Chunk = LpdScanChunk<MP_T, MP_CH, MP_CAP>;
 typedef unsigned long long u64;
 
 __global__ __launch_bounds__(MP_T) void correct_kernel(const double* __restrict__ poses, const long long* __restrict__ D, int S,
@@ -73,22 +75,6 @@ __device__ __forceinline__ int mp_global_insert(long long* __restrict__ keys, lo
     return 0;
 }
 
-// n floats global -> LDS: scalar elements up to the first 16-byte boundary of the global side, 16-byte loads on the body, scalar
-// elements behind it.  Nothing outside [g, g + n) is read.
-__device__ __forceinline__ void mp_copy_in(const float* __restrict__ g, float* s, int n, int tid)
-{
-    int head = (int)((4u - (unsigned)(((uintptr_t)g >> 2) & 3u)) & 3u);
-    head = head < n ? head : n;
-    const int body = (n - head) >> 2, tail0 = head + 4 * body;
-    if (tid < head) s[tid] = g[tid];
-    for (int v = tid; v < body; v += MP_T) {
-        const float4 a = *reinterpret_cast<const float4*>(g + head + 4 * v);
-        float* d = s + head + 4 * v;
-        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
-    }
-    if (tid < n - tail0) s[tail0 + tid] = g[tail0 + tid];
-}
-
 template <bool DIRECT>
 __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ points, int ld, int rows, const int32_t* __restrict__ offsets,
                                                       const double* __restrict__ poses, int scan0, int scan1, const double* __restrict__ origin,
@@ -115,8 +101,7 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
             lkey[s] = (u64)LPD_MAP_EMPTY;
             lacc[4 * s + 0] = 0; lacc[4 * s + 1] = 0; lacc[4 * s + 2] = 0; lacc[4 * s + 3] = 0;
         }
-    if (tid == 0) span[0] = lpd_drive_scan_of(offsets, scan0, scan1, g0);
-    if (tid == 64) span[1] = lpd_drive_scan_of(offsets, scan0, scan1, g1 - 1);
+    Chunk::find_span(offsets, scan0, scan1, g0, cn, span, tid);
     __syncthreads();
     const int i_lo = span[0], i_hi = span[1];      // both in [scan0, scan1 - 1]
     // is this part of the table one?  (lpd_map_chunk_ok, its loop shared among the threads)
@@ -127,35 +112,11 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
         if (tid == 0) atomicAdd((u64*)info + 1, (u64)cn);
         return;
     }
-    const float* src = points + (size_t)g0 * ld;
-    if (ld == 3) {
-        mp_copy_in(src, buf, 3 * cn, tid);
-    } else if (ld == 4 && ((uintptr_t)points & 15) == 0) {
-#pragma unroll
-        for (int k = 0; k < MP_R; ++k) {
-            const int j = k * MP_T + tid;
-            if (j < cn) {
-                const float4 a = *reinterpret_cast<const float4*>(src + (size_t)j * 4);
-                buf[3 * j + 0] = a.x; buf[3 * j + 1] = a.y; buf[3 * j + 2] = a.z;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < MP_R; ++k) {
-            const int j = k * MP_T + tid;
-            if (j < cn) {
-                const float* p = src + (size_t)j * ld;
-                buf[3 * j + 0] = p[0]; buf[3 * j + 1] = p[1]; buf[3 * j + 2] = p[2];
-            }
-        }
-    }
+    Chunk::load(points, ld, g0, cn, buf, tid);
     const int ns = i_hi - i_lo + 1;
-    const bool table = ns <= MP_CAP;
     const double org[3] = {origin[0], origin[1], origin[2]};
-    if (table) {
-        if (tid < ns) rel[tid] = lpd_map_rel(poses + (size_t)12 * (i_lo + tid), org);
-        if (tid <= ns) soff[tid] = offsets[i_lo + tid];      // i_lo + ns = i_hi + 1 <= scan1
-    }
+    const auto pose = [&](int i) { return lpd_map_rel(poses + (size_t)12 * i, org); };
+    const bool table = Chunk::poses(offsets, i_lo, ns, rel, soff, tid, pose);      // i_lo + ns = i_hi + 1 <= scan1
     __syncthreads();
     u64 n_ins = 0, n_drop = 0, n_lost = 0, n_new = 0;
 #pragma unroll
@@ -165,14 +126,7 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
             const float x = buf[3 * j + 0], y = buf[3 * j + 1], z = buf[3 * j + 2];
             float w[3];
             int64_t key, U[3];
-            int ok;
-            if (table) {
-                ok = lpd_map_row(rel[lpd_drive_scan_of(soff, 0, ns, g0 + j)], inv_cell, x, y, z, w, &key, U);
-            } else {
-                const int i = lpd_drive_scan_of(offsets, i_lo, i_hi + 1, g0 + j);
-                ok = lpd_map_row(lpd_map_rel(poses + (size_t)12 * i, org), inv_cell, x, y, z, w, &key, U);
-            }
-            if (!ok) {
+            if (!lpd_map_row(Chunk::row_pose(table, rel, soff, offsets, i_lo, ns, g0 + j, pose), inv_cell, x, y, z, w, &key, U)) {
                 ++n_drop;
                 continue;
             }

@@ -13,20 +13,17 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
 #include "lpd_drive_math.h"
 #include "lpd_pgo_math.h"
 
 #define LPD_MAP_FN LPD_DRIVE_FN
 
-#define LPD_MAP_QLIM 1048576                 // 2^20: a cell index lies in [-2^20, 2^20)
-#define LPD_MAP_QLIM_F 1048576.0f
+// LPD_MAP_QLIM, LPD_MAP_CHUNK, LPD_MAP_MAX_PROBES, LPD_MAP_MIN_CAPACITY and LPD_MAP_MAX_CAPACITY are the public header's
+#define LPD_MAP_QLIM_F 1048576.0f            // LPD_MAP_QLIM
 #define LPD_MAP_UNITS 65536.0                // fixed-point units per metre, those of the drive step
-#define LPD_MAP_CHUNK 1024                   // input rows of one workgroup: chunk c is the rows 1024 c .. 1024 c + 1023 of the table
 #define LPD_MAP_LDS_SLOTS 1024               // slots of a workgroup's own table (a power of two)
 #define LPD_MAP_LDS_PROBES 8                 // probes there before a row goes straight to the caller's table
-#define LPD_MAP_MAX_PROBES 128               // probes in the caller's table before a row is lost (never more than its capacity)
-#define LPD_MAP_MIN_CAPACITY 16
-#define LPD_MAP_MAX_CAPACITY (1LL << 36)
 #define LPD_MAP_EMPTY (-1LL)                 // the key of an empty slot
 // cell = 1 / inv_cell lies in [2^-10, 16] m.  A row that gets a cell has |fl(w * inv_cell)| <= 2^20, so |w| <= 2^20 * 16 * (1 + 2^-24)
 // = 2^24 + 1 and |U| = |rint(w * 65536)| < 2^41: the sum of FEWER THAN 2^22 ROWS IN ONE CELL cannot leave an int64 wherever the cell

@@ -8,17 +8,17 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_PLACES_FN __host__ __device__ __forceinline__
 #else
 #define LPD_PLACES_FN static inline
 #endif
 
-#define LPD_PLACES_MAX_ITEMS (1 << 22)      // Q and D
-#define LPD_PLACES_MAX_SEGMENTS 4096        // S (one grid dimension)
+// LPD_PLACES_MAX_ITEMS, LPD_PLACES_MAX_SEGMENTS and LPD_PLACES_CHUNK are the public header's
 #define LPD_PLACES_WAVE_QUERIES 4           // query rows a wave carries
 #define LPD_PLACES_BLOCK_QUERIES 16         // ... and a 256-thread workgroup: four waves
-#define LPD_PLACES_CHUNK 1024               // candidate positions staged in LDS at a time (16 KiB)
 
 // the right-hand side of the comparison: ONE product
 LPD_PLACES_FN double lpd_place_radius_sq(double r) { return r * r; }

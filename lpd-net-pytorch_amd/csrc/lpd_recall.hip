@@ -30,7 +30,7 @@ namespace {
 constexpr int RP_THREADS = 256;
 constexpr int RP_QT = 128;         // queries per workgroup (32 per wave)
 constexpr int RP_DT = 32;          // database rows per tile
-constexpr int RP_KMAX = 64;
+constexpr int RP_KMAX = LPD_RECALL_KMAX;
 
 __global__ void recall_rownorm_kernel(const float* __restrict__ X, int ld, int n, int dim, float* __restrict__ out)
 {

@@ -11,19 +11,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_SEQ_FN __host__ __device__ __forceinline__
 #else
 #define LPD_SEQ_FN static inline
 #endif
 
-// (LPD_SEQ_BAND, LPD_SEQ_QBITS, LPD_SEQ_KMAX, LPD_SEQ_MAX_HYP are the public header's; repeated for a host program that has only this file)
-#ifndef LPD_SEQ_BAND
-#define LPD_SEQ_BAND 15                   // a candidate's block holds the database rows j - 15 .. j + 15
-#define LPD_SEQ_QBITS 14                  // the quantum of a squared distance is 2^-14
-#define LPD_SEQ_KMAX 64
-#define LPD_SEQ_MAX_HYP 1024
-#endif
+// LPD_SEQ_BAND (a candidate's block holds the database rows j - 15 .. j + 15), LPD_SEQ_QBITS (the quantum of a squared distance is
+// 2^-14), LPD_SEQ_KMAX and LPD_SEQ_MAX_HYP are the public header's
 #define LPD_SEQ_CLAMP 16.0f               // a squared distance is clamped at 16: dq <= 2^18, a sum of 31 terms < 2^23
 #define LPD_SEQ_QUANT 16384.0f            // 2^LPD_SEQ_QBITS
 #define LPD_SEQ_TILE 32                   // the block is [32][32]; row 31 and column 31 are -1

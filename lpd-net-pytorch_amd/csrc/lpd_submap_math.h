@@ -9,6 +9,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_SUBMAP_FN __host__ __device__ __forceinline__
 #else
@@ -16,9 +18,7 @@
 #endif
 
 #define LPD_SUBMAP_RUNGS 128                 // j = 0 .. 127
-#define LPD_SUBMAP_MIN_N 128                 // rung 127 has at most 125 cells, so the search cannot fail for N >= 128
-#define LPD_SUBMAP_MAX_N 4096
-#define LPD_SUBMAP_MAX_POINTS (1 << 20)      // raw points per cloud: 2^20 points x 2^20 quantisation steps stay far inside 64 bits
+// LPD_SUBMAP_MIN_N, LPD_SUBMAP_MAX_N and LPD_SUBMAP_MAX_POINTS are the public header's
 #define LPD_SUBMAP_QBITS 20                  // u = rint((x - mn) * 2^20 / E)
 
 // 2^(-i/16) rounded to fp32, i = 0 .. 15

@@ -9,16 +9,15 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/lpd_hip.h"      // the limits a caller meets: plain C
+
 #if defined(__HIPCC__)
 #define LPD_TUPLE_FN __host__ __device__ __forceinline__
 #else
 #define LPD_TUPLE_FN static inline
 #endif
 
-#define LPD_TUPLE_MAX_ITEMS 262144      // T: the membership bitmap (32 KiB) and its scanned popcounts (32 KiB) live in LDS
-#define LPD_TUPLE_MAX_SAMPLES 4096      // m
-#define LPD_TUPLE_MAX_LISTS 64          // L and X
-#define LPD_TUPLE_MAX_ROWS 65535        // R, and B of lpd_gather_tuples (one grid dimension)
+// LPD_TUPLE_MAX_ITEMS, LPD_TUPLE_MAX_SAMPLES, LPD_TUPLE_MAX_LISTS and LPD_TUPLE_MAX_ROWS are the public header's
 
 // ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), published constants
 #define LPD_PHILOX_M0 0xD2511F53u

@@ -19,6 +19,7 @@ import torch
 
 from . import ops, submap
 from ._lib import LpdHipError
+from .submap import _lengths
 
 FRAMES = {"world": 0, "reference": 1}
 
@@ -112,25 +113,8 @@ def plan_windows(poses, length=20.0, stride=10.0, device=None, lengths=None):
     return _plan(p, lengths, length, stride)
 
 
-def _lengths(lengths, S, what):
-    """-> the rows of every scan as a numpy int64 array (a numpy array passes through: no per-element work for a long drive)"""
-    a = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
-    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-        raise ValueError(f"{what}: lengths must be a sequence of integers, got {a.dtype} {a.shape}")
-    a = a.astype(np.int64, copy=False)
-    if S is not None and a.size != S:
-        raise ValueError(f"{what}: {a.size} scan lengths for {S} poses")
-    if a.size and int(a.min()) < 0:
-        raise ValueError(f"{what}: a scan length is negative")
-    return a
-
-
 def _scan_offsets(lengths, device):
-    off = np.zeros(len(lengths) + 1, dtype=np.int64)
-    np.cumsum(lengths, out=off[1:])
-    if off[-1] >= 1 << 31:
-        raise ValueError(f"a drive of {int(off[-1])} rows in one call exceeds 2^31")
-    return torch.from_numpy(off.astype(np.int32)).to(device, non_blocking=True)
+    return submap._offsets_of(lengths, device, "a drive of {} rows in one call exceeds 2^31")
 
 
 class DriveRows:
@@ -206,21 +190,8 @@ def accumulate(points, lengths, poses=None, plan=None, length=20.0, stride=10.0,
 
 
 def _drive_input(points, lengths):
-    """as submap._gather_input, but a scan of a drive may have no rows"""
-    if lengths is None:
-        if isinstance(points, (torch.Tensor, np.ndarray)):
-            points = [points] if points.ndim == 2 else list(points)
-        scans = [submap._as_tensor(s, f"scan {i}") for i, s in enumerate(points)]
-        if not scans:
-            raise ValueError("accumulate: no scans")
-        if len({(s.dtype, s.device) for s in scans}) != 1:
-            raise ValueError("accumulate: the scans of one drive must share dtype and device")
-        return (scans[0] if len(scans) == 1 else torch.cat([s[:, :3] for s in scans], 0)), np.array([s.shape[0] for s in scans], dtype=np.int64)
-    pts = submap._as_tensor(points, "points")
-    lengths = _lengths(lengths, None, "accumulate")
-    if not lengths.size or int(lengths.sum()) != pts.shape[0]:
-        raise ValueError(f"accumulate: lengths must be non-negative and sum to the {pts.shape[0]} rows of points")
-    return pts, lengths
+    """submap._gather_input for the scans of a drive: one may have no rows"""
+    return submap._gather_input(points, lengths, "accumulate", empty_ok=True)
 
 
 def submaps_from_drive(points, lengths, poses, length=20.0, stride=10.0, num_points=submap.NUM_POINTS, clean=None, frame="reference",

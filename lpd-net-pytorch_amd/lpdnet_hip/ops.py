@@ -10,7 +10,13 @@ import torch
 
 from . import _debug, _lib
 
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = (_lib.DEFINES["LPD_ACT_" + n] for n in ("NONE", "RELU", "LEAKY", "SIGMOID"))
+
+def _defines(prefix, *names):
+    """the integer limits LPD_<prefix>_<name> of include/lpd_hip.h: a limit that a wrapper enforces is defined there, once"""
+    return tuple(_lib.DEFINES[f"LPD_{prefix}_{n}"] for n in names)
+
+
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = _defines("ACT", "NONE", "RELU", "LEAKY", "SIGMOID")
 
 class _PerThread(__import__("threading").local):
     """Measurement hooks, per host thread (a profile opened by one thread must not collect another thread's launches); read and
@@ -150,6 +156,15 @@ def _rows(t, name):
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected a 2-D tensor with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
     return t.stride(0)
+
+
+def _scan_points(what, points):
+    """the points of a ragged scan table for the caller `what`: fp32 on the device, [rows, >=3] with unit column stride and 1 <= rows <
+    2^31 -> the row stride ld"""
+    ld = _rows(points, "points")
+    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    return ld
 
 
 def _vec(t, name, n):
@@ -1167,7 +1182,7 @@ def local_features(xyz_rows, idx, B, N, *, candidates=None, columns=range(10), c
     return (out, kopt) if want_k else out
 
 
-SUBMAP_MIN_N, SUBMAP_MAX_N, SUBMAP_MAX_POINTS = 128, 4096, 1 << 20
+SUBMAP_MIN_N, SUBMAP_MAX_N, SUBMAP_MAX_POINTS = _defines("SUBMAP", "MIN_N", "MAX_N", "MAX_POINTS")
 
 
 def check_submap_lengths(lengths, rows=None, what="make_submaps"):
@@ -1229,7 +1244,7 @@ def make_submaps(points, offsets, B, N, normalize=True, want_counts=False, out=N
     return _make_submaps(points, offsets, B, N, normalize, want_counts, out)
 
 
-TUPLE_MAX_ITEMS, TUPLE_MAX_SAMPLES, TUPLE_MAX_LISTS, TUPLE_MAX_ROWS = 262144, 4096, 64, 65535      # csrc/lpd_tuple_math.h
+TUPLE_MAX_ITEMS, TUPLE_MAX_SAMPLES, TUPLE_MAX_LISTS, TUPLE_MAX_ROWS = _defines("TUPLE", "MAX_ITEMS", "MAX_SAMPLES", "MAX_LISTS", "MAX_ROWS")
 
 
 def sample_items(off, idx, T, lists, extra, m, invert, seed):
@@ -1305,7 +1320,7 @@ def gather_tuples(table, items, rot=None, sigma=0.0, clip=0.05, seed=0, out=None
     return out
 
 
-PLACES_MAX_ITEMS, PLACES_MAX_SEGMENTS, PLACES_CHUNK = 1 << 22, 4096, 1024      # csrc/lpd_places_math.h
+PLACES_MAX_ITEMS, PLACES_MAX_SEGMENTS, PLACES_CHUNK = _defines("PLACES", "MAX_ITEMS", "MAX_SEGMENTS", "CHUNK")
 
 
 def radius_lists(qpos, dpos, radius, seg_off=None, skip_seg=None, self_item=None):
@@ -1364,8 +1379,8 @@ def radius_lists(qpos, dpos, radius, seg_off=None, skip_seg=None, self_item=None
     return off, idx, counts
 
 
-CLEAN_MAX_H, CLEAN_MAX_RANGE = 1024, 512.0      # csrc/lpd_clean_math.h
-CLEAN_CHUNK = _lib.DEFINES["LPD_CLEAN_CHUNK"]
+CLEAN_MAX_H, CLEAN_CHUNK = _defines("CLEAN", "MAX_H", "CHUNK")
+CLEAN_MAX_RANGE = 512.0      # csrc/lpd_clean_math.h
 
 
 class CleanParams(ctypes.Structure):
@@ -1384,14 +1399,11 @@ def _clean_head(what, points, offsets, B, max_len, params):
     if not isinstance(params, CleanParams):
         raise TypeError(f"{what}: params must be an ops.CleanParams (submap.RoadRemoval().c_params())")
     B, max_len = int(B), int(max_len)
-    ld = _rows(points, "points")
-    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
-        raise ValueError(f"{what}: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
-    if not 1 <= B <= 65535 or offsets.dim() != 1 or offsets.numel() != B + 1:
-        raise ValueError(f"{what}: offsets must hold B+1 entries with 1 <= B <= 65535, got B={B} and {tuple(offsets.shape)}")
+    ld = _scan_points(what, points)
+    # a B outside its range fails with the same words: no tensor holds -1 entries
+    offsets = _drive_offsets(what, offsets, B if 1 <= B <= 65535 else -2, f"B+1 entries with 1 <= B <= 65535, got B={B} and ")
     if not 1 <= max_len <= SUBMAP_MAX_POINTS:
         raise ValueError(f"{what}: max_len={max_len} outside 1 .. 2^20")
-    offsets = offsets.contiguous()
     return (_ptr(points), ld, points.shape[0], _ptr(offsets), B, max_len, ctypes.byref(params)), B, max_len
 
 
@@ -1438,7 +1450,7 @@ def clean_scans(points, offsets, B, max_len, params, plane=None, info=None, want
     return out, out_offsets, mask
 
 
-DRIVE_MAX_SCANS, DRIVE_MAX_WINDOWS, DRIVE_MAX_WINDOW_NO, DRIVE_MAX_UNITS = 1 << 22, 65535, 1 << 22, 1 << 40      # csrc/lpd_drive_math.h
+DRIVE_MAX_SCANS, DRIVE_MAX_WINDOWS, DRIVE_MAX_WINDOW_NO, DRIVE_MAX_UNITS = _defines("DRIVE", "MAX_SCANS", "MAX_WINDOWS", "MAX_WINDOW_NO", "MAX_UNITS")
 DRIVE_UNITS_PER_METRE = 65536
 
 
@@ -1471,10 +1483,12 @@ def drive_distance(poses):
     return q, torch.cumsum(q, 0)
 
 
-def _drive_offsets(what, offsets, S):
+def _drive_offsets(what, offsets, S, must=None):
+    """the offsets of a ragged scan table for the caller `what`: int32 on the device, [S+1] -> contiguous.  must: the caller's own
+    words for what they must hold, up to the shape it got"""
     _req(offsets, "offsets", torch.int32)
     if offsets is None or offsets.dim() != 1 or offsets.numel() != S + 1:
-        raise ValueError(f"{what}: offsets must hold S+1 = {S + 1} entries, got {None if offsets is None else tuple(offsets.shape)}")
+        raise ValueError(f"{what}: offsets must hold {must or f'S+1 = {S + 1} entries, got '}{None if offsets is None else tuple(offsets.shape)}")
     return offsets.contiguous()
 
 
@@ -1511,9 +1525,7 @@ def drive_rows(points, offsets, poses, plan, out_off, max_len, out_rows, frame=1
     poses, S = _drive_poses("drive_rows", poses)
     if points is None or plan is None or out_off is None:
         raise TypeError("drive_rows: points, plan and out_off are tensors")
-    ld = _rows(points, "points")
-    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
-        raise ValueError(f"drive_rows: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    ld = _scan_points("drive_rows", points)
     offsets = _drive_offsets("drive_rows", offsets, S)
     if plan.dim() != 2 or plan.shape[1] != 4 or not 1 <= plan.shape[0] <= DRIVE_MAX_WINDOWS:
         raise ValueError(f"drive_rows: plan must be [W, 4] with 1 <= W <= {DRIVE_MAX_WINDOWS}, got {tuple(plan.shape)}")
@@ -1539,9 +1551,9 @@ def drive_rows(points, offsets, poses, plan, out_off, max_len, out_rows, frame=1
     return out
 
 
-# the drive map (csrc/lpd_map.hip); the numbers are those of csrc/lpd_map_math.h
-MAP_CHUNK, MAP_MAX_PROBES, MAP_MIN_CAPACITY, MAP_MAX_CAPACITY, MAP_QLIM = 1024, 128, 16, 1 << 36, 1 << 20
-MAP_MIN_CELL, MAP_MAX_CELL = 2.0 ** -10, 16.0
+# the drive map (csrc/lpd_map.hip)
+MAP_CHUNK, MAP_MAX_PROBES, MAP_MIN_CAPACITY, MAP_MAX_CAPACITY, MAP_QLIM = _defines("MAP", "CHUNK", "MAX_PROBES", "MIN_CAPACITY", "MAX_CAPACITY", "QLIM")
+MAP_MIN_CELL, MAP_MAX_CELL = 2.0 ** -10, 16.0      # csrc/lpd_map_math.h
 MAP_UNITS_PER_METRE = 65536
 
 
@@ -1629,9 +1641,7 @@ def map_insert(points, offsets, poses, origin, inv_cell, keys, acc, info, scan0=
     poses, S = _drive_poses(what, poses)
     if points is None or origin is None:
         raise TypeError(f"{what}: points and origin are tensors")
-    ld = _rows(points, "points")
-    if points.shape[1] < 3 or ld < 3 or points.shape[0] < 1 or points.shape[0] >= 1 << 31:
-        raise ValueError(f"{what}: points must be [rows, >=3] with 1 <= rows < 2^31, got {tuple(points.shape)}")
+    ld = _scan_points(what, points)
     offsets = _drive_offsets(what, offsets, S)
     if tuple(origin.shape) != (3,):
         raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
@@ -1666,8 +1676,8 @@ def map_rehash(keys_in, acc_in, keys, acc, info):
 # ------------------------------------------------------------------------------------------------
 # geometric verification of retrieved places (csrc/lpd_align.hip)
 # ------------------------------------------------------------------------------------------------
-ALIGN_GRID, ALIGN_MAX_S, ALIGN_MAX_LAYERS, ALIGN_MAX_H, ALIGN_MAX_R = 128, 16, 4, 1024, 8192      # csrc/lpd_align_math.h
-ALIGN_MAX_POINTS, ALIGN_MAX_PAIRS = 16384, 1 << 20
+ALIGN_GRID, ALIGN_MAX_S, ALIGN_MAX_LAYERS, ALIGN_MAX_H, ALIGN_MAX_R = _defines("ALIGN", "GRID", "MAX_S", "MAX_LAYERS", "MAX_H", "MAX_R")
+ALIGN_MAX_POINTS, ALIGN_MAX_PAIRS = _defines("ALIGN", "MAX_POINTS", "MAX_PAIRS")
 
 
 def _tensor_arg(what, t, name, dtype, optional=False):
@@ -1764,7 +1774,8 @@ def align_pairs(a, b, pairs, rot, H, inv_cell, S, z0, inv_zcell, layers, scale_a
 # ------------------------------------------------------------------------------------------------
 # refinement of a verified match to a 6-DoF pose (csrc/lpd_icp.hip)
 # ------------------------------------------------------------------------------------------------
-ICP_MAX_POINTS, ICP_MAX_PAIRS, ICP_MAX_ITERS, ICP_MIN_INLIERS, ICP_MAX_DMAX, ICP_SUMS = 16384, 1 << 20, 64, 6, 16.0, 32      # csrc/lpd_icp_math.h
+ICP_MAX_POINTS, ICP_MAX_PAIRS, ICP_MAX_ITERS, ICP_MIN_INLIERS, ICP_SUMS = _defines("ICP", "MAX_POINTS", "MAX_PAIRS", "MAX_ITERS", "MIN_INLIERS", "SUMS")
+ICP_MAX_DMAX = 16.0      # csrc/lpd_icp_math.h
 
 
 def point_normals(xyz_rows, idx, B, N, want_flatness=False):
@@ -2104,7 +2115,7 @@ def bn_train_stats(X, bn, rows=None):
 STATS_IN_GEMM = _debug.on("gemm-stats")
 
 
-STAT_CMAX = 1024      # columns of the statistics workspace (csrc/lpd_common.h LPD_STAT_CMAX): lpd_gemm_x3w_stats refuses wider layers
+STAT_CMAX, = _defines("STAT", "CMAX")      # columns of the statistics workspace: lpd_gemm_x3w_stats refuses wider layers
 
 
 def linear_bn_stats_fused_applies(M, N, K):
@@ -3005,7 +3016,7 @@ def retrieval_topk(Q, D, k):
 
 
 RecallPairs = __import__("collections").namedtuple("RecallPairs", "first one_pct top1_sim hist n_eval n_onepct out_off topk_idx")
-RECALL_KMAX = 64
+RECALL_KMAX, = _defines("RECALL", "KMAX")
 
 
 def _index_array(x, name, ndim):

@@ -55,28 +55,48 @@ def _as_tensor(a, what):
     return t
 
 
-def _gather_input(scans_or_points, lengths):
-    """-> (points [rows, >=3] tensor on the caller's device, host lengths)"""
+def _lengths(lengths, S, what):
+    """-> the rows of every scan as a numpy int64 array (a numpy array passes through: no per-element work for a long drive)"""
+    a = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError(f"{what}: lengths must be a sequence of integers, got {a.dtype} {a.shape}")
+    a = a.astype(np.int64, copy=False)
+    if S is not None and a.size != S:
+        raise ValueError(f"{what}: {a.size} scan lengths for {S} poses")
+    if a.size and int(a.min()) < 0:
+        raise ValueError(f"{what}: a scan length is negative")
+    return a
+
+
+def _gather_input(scans_or_points, lengths, what="make_submaps", empty_ok=False):
+    """-> (points [rows, >=3] tensor on the caller's device, host lengths) for the caller `what`.  Every scan has 1 .. 2^20 rows and the
+    lengths come back as a list; empty_ok: the scans of a drive, of which one may have no rows and whose lengths come back as a numpy
+    int64 array (_lengths)."""
     if lengths is None:
         if isinstance(scans_or_points, (torch.Tensor, np.ndarray)):
             scans_or_points = [scans_or_points] if scans_or_points.ndim == 2 else list(scans_or_points)
         scans = [_as_tensor(s, f"scan {i}") for i, s in enumerate(scans_or_points)]
         if not scans:
-            raise ValueError("make_submaps: no scans")
+            raise ValueError(f"{what}: no scans")
         lengths = [int(s.shape[0]) for s in scans]
-        ops.check_submap_lengths(lengths)
-        if len(scans) == 1:
-            return scans[0], lengths
+        if not empty_ok:
+            ops.check_submap_lengths(lengths, None, what)
         if len({(s.dtype, s.device) for s in scans}) != 1:
-            raise ValueError("make_submaps: the scans of one batch must share dtype and device")
-        return torch.cat([s[:, :3] for s in scans], 0), lengths
+            raise ValueError(f"{what}: the scans of one {'drive' if empty_ok else 'batch'} must share dtype and device")
+        points = scans[0] if len(scans) == 1 else torch.cat([s[:, :3] for s in scans], 0)
+        return points, np.array(lengths, dtype=np.int64) if empty_ok else lengths
     points = _as_tensor(scans_or_points, "points")
+    if empty_ok:
+        lengths = _lengths(lengths, None, what)
+        if not lengths.size or int(lengths.sum()) != points.shape[0]:
+            raise ValueError(f"{what}: lengths must be non-negative and sum to the {points.shape[0]} rows of points")
+        return points, lengths
     lengths = [int(n) for n in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
     if not lengths:
-        raise ValueError("make_submaps: no scans")
-    total = ops.check_submap_lengths(lengths, points.shape[0])
+        raise ValueError(f"{what}: no scans")
+    total = ops.check_submap_lengths(lengths, points.shape[0], what)
     if total != points.shape[0]:
-        raise ValueError(f"make_submaps: lengths sum to {total}, points has {points.shape[0]} rows")
+        raise ValueError(f"{what}: lengths sum to {total}, points has {points.shape[0]} rows")
     return points, lengths
 
 
@@ -165,11 +185,12 @@ class CleanedScans:
         return torch.diff(self.offsets).cpu().tolist()
 
 
-def _offsets_of(lengths, device):
+def _offsets_of(lengths, device, too_many="make_submaps: {} rows in one batch exceed 2^31"):
+    """host lengths -> the scan table's offsets [len + 1] int32 on the device; too_many: the caller's message for 2^31 rows and more"""
     off = np.zeros(len(lengths) + 1, dtype=np.int64)
     np.cumsum(lengths, out=off[1:])
     if off[-1] >= 1 << 31:
-        raise ValueError(f"make_submaps: {int(off[-1])} rows in one batch exceed 2^31")
+        raise ValueError(too_many.format(int(off[-1])))
     return torch.from_numpy(off.astype(np.int32)).to(device, non_blocking=True)
 
 

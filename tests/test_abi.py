@@ -130,6 +130,22 @@ def test_defines_equal_the_compilers(compiler_view):
             "LPD_KNN_PM_PREPARED", "LPD_CLEAN_CHUNK"} <= set(got)
     assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY, ops.ACT_SIGMOID) == tuple(got["LPD_ACT_" + n] for n in ("NONE", "RELU", "LEAKY", "SIGMOID"))
     assert (ops.KNN_PM_PREPARED, ops.CLEAN_CHUNK) == (got["LPD_KNN_PM_PREPARED"], got["LPD_CLEAN_CHUNK"])
+    # every integer limit that a wrapper enforces: defined in the public header, and ops holds the compiler's value under its name
+    assert set(WRAPPER_LIMITS) <= set(_lib.DEFINES)
+    for name in WRAPPER_LIMITS:
+        assert getattr(ops, name[len("LPD_"):]) == got[name], name
+
+
+WRAPPER_LIMITS = [
+    "LPD_SUBMAP_MIN_N", "LPD_SUBMAP_MAX_N", "LPD_SUBMAP_MAX_POINTS",
+    "LPD_TUPLE_MAX_ITEMS", "LPD_TUPLE_MAX_SAMPLES", "LPD_TUPLE_MAX_LISTS", "LPD_TUPLE_MAX_ROWS",
+    "LPD_PLACES_MAX_ITEMS", "LPD_PLACES_MAX_SEGMENTS", "LPD_PLACES_CHUNK",
+    "LPD_CLEAN_MAX_H",
+    "LPD_DRIVE_MAX_SCANS", "LPD_DRIVE_MAX_WINDOWS", "LPD_DRIVE_MAX_WINDOW_NO", "LPD_DRIVE_MAX_UNITS",
+    "LPD_MAP_CHUNK", "LPD_MAP_MAX_PROBES", "LPD_MAP_MIN_CAPACITY", "LPD_MAP_MAX_CAPACITY", "LPD_MAP_QLIM",
+    "LPD_ALIGN_GRID", "LPD_ALIGN_MAX_S", "LPD_ALIGN_MAX_LAYERS", "LPD_ALIGN_MAX_H", "LPD_ALIGN_MAX_R", "LPD_ALIGN_MAX_POINTS", "LPD_ALIGN_MAX_PAIRS",
+    "LPD_ICP_MAX_POINTS", "LPD_ICP_MAX_PAIRS", "LPD_ICP_MAX_ITERS", "LPD_ICP_MIN_INLIERS", "LPD_ICP_SUMS",
+    "LPD_STAT_CMAX", "LPD_RECALL_KMAX"]
 
 
 # ---- the reader on strings ----

@@ -427,7 +427,9 @@ def test_public_surface():
     assert '#include "lpd_tuple_math.h"' in math_h and "LPD_PHILOX_M0" not in math_h      # the generator is reused, not copied
     import re
     assert not re.search(r"\bfmaf?\s*\(", math_h) and "__HIPCC__" in math_h
-    for define in ("LPD_CLEAN_MAX_H 1024", "LPD_CLEAN_CHUNK 1024", "LPD_CLEAN_MAX_RANGE 512.0f", "LPD_CLEAN_MAX_POINTS (1 << 20)"):
+    for define in ("LPD_CLEAN_MAX_H 1024", "LPD_CLEAN_CHUNK 1024"):      # the limits a wrapper enforces: the public header's, once
+        assert "#define " + define in hdr and "#define " + define.split()[0] not in math_h
+    for define in ("LPD_CLEAN_MAX_RANGE 512.0f", "LPD_CLEAN_MAX_POINTS (1 << 20)"):
         assert "#define " + define in math_h
     kern = open(os.path.join(CSRC, "lpd_clean.hip")).read()
     assert "atomicAdd" in kern and not re.search(r"\bfmaf?\s*\(", kern)

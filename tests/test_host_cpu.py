@@ -209,7 +209,7 @@ def test_fused_statistics_gates_stop_at_the_workspace_width():
     assert ops.STAT_CMAX == 1024
     assert ops.linear_bn_stats_fused_applies(44 * 4096, 1024, 512)
     assert not ops.linear_bn_stats_fused_applies(44 * 4096, 2048, 512)
-    src = open(os.path.join(ROOT, "lpd-net-pytorch_amd", "csrc", "lpd_common.h")).read()
+    src = open(os.path.join(ROOT, "include", "lpd_hip.h")).read()      # the kernels' value: csrc/lpd_common.h takes it from there
     assert re.search(r"#define\s+LPD_STAT_CMAX\s+1024\b", src)
 
 

@@ -282,8 +282,8 @@ def test_public_surface():
     math = open(MATH_H).read()
     assert "(dx * dx) + (dy * dy) <= r2" in math and "fma" not in math.replace("fused multiply-add", "")
     assert (ops.PLACES_MAX_ITEMS, ops.PLACES_MAX_SEGMENTS, ops.PLACES_CHUNK) == (1 << 22, 4096, 1024)
-    for define in ("LPD_PLACES_MAX_ITEMS (1 << 22)", "LPD_PLACES_MAX_SEGMENTS 4096", "LPD_PLACES_CHUNK 1024"):
-        assert "#define " + define in math
+    for define in ("LPD_PLACES_MAX_ITEMS 4194304", "LPD_PLACES_MAX_SEGMENTS 4096", "LPD_PLACES_CHUNK 1024"):
+        assert "#define " + define in hdr and "#define " + define.split()[0] not in math      # the public header's, once
     assert [a for a in inspect.signature(ops.radius_lists).parameters] == ["qpos", "dpos", "radius", "seg_off", "skip_seg", "self_item"]
     sig = inspect.signature(places.training_lists)
     assert [a for a in sig.parameters] == ["positions", "pos_radius", "near_radius", "device"]
