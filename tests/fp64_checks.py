@@ -10,6 +10,9 @@ U23 = 2.0 ** -23
 ELEM_X = 4.0
 SUM_X = 2.0
 X3_TERM = 3 * 2.0 ** -18       # split-bf16 three-product form: |a b - (ah bh + ah bl + al bh)| <= (2^-18 + 2 * 2^-18) |a b|
+X1_TERM = 2 * 2.0 ** -9 + 2.0 ** -18      # one product ah bh: both operands rounded to bf16
+X2_TERM = 2.0 ** -18                      # bf16 rows (exact) against a split operand: only that operand's residual is lost
+AFFINE_TERM = 2.0 ** -22                  # operand transform evaluated in fp32 in a loader (tests/test_gemm_routes_gpu.py derives the three)
 NONE, RELU, LEAKY, SIGMOID = 0, 1, 2, 3
 SLOPE = 0.01
 

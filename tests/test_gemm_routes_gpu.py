@@ -63,13 +63,10 @@ import pytest
 import torch
 
 import gemm_routes as gr
-from fp64_checks import NONE, SLOPE, X3_TERM, _act, _act_scale, _seqsum, check_bound, seq_matmul
+from fp64_checks import AFFINE_TERM, NONE, SLOPE, X1_TERM, X2_TERM, X3_TERM, _act, _act_scale, _seqsum, check_bound, seq_matmul
 
 pytestmark = pytest.mark.gpu
 
-X1_TERM = 2 * 2.0 ** -9 + 2.0 ** -18
-X2_TERM = 2.0 ** -18
-AFFINE_TERM = 2.0 ** -22
 PAD = 1e4          # what operand padding and unused panels hold
 FILL = -7.0        # what the surroundings of an output hold
 

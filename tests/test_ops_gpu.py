@@ -1035,13 +1035,18 @@ def test_windowed_kagg_is_bit_identical(cuda, C, N, k, B, graph):
 
 
 @pytest.mark.parametrize("M,KA,KB", [(8192, 128, 64), (20000, 256, 128), (4096 + 37, 1024, 512), (70000, 512, 128),
-                                     (16384, 1024, 512), (8352, 256, 256), (33 * 1024 + 32, 512, 256),   # the last three: 256 x 256 tiles
+                                     # the next three satisfy gemm_tn_256(), but tn_tr_tb() takes them first: gemm_tn_tr_kernel<false, 256>.
+                                     # gemm_tn_x3_256_kernel runs under LPD_DEBUG=tn-tr=0 only (tests/tn_routes.py, tests/test_tn_routes_gpu.py)
+                                     (16384, 1024, 512), (8352, 256, 256), (33 * 1024 + 32, 512, 256),
                                      (16384, 512, 64), (2048, 256, 192)])
 def test_gemm_tn_weight_gradient_kernel(cuda, M, KA, KB):
     """lpd_gemm_tn: dW = A^T B over the rows (register-transposed staging, split-bf16): fp32-grade against fp64, ragged row
     counts, column-slice operands, and agreement with the generic k-major product.  Products with KA % 256 == 0 over whole 32-row
-    chunks run on the transposed-read kernel (gemm_tn_tr_kernel: 256-, 128- and 64-wide b tiles, odd and even chunk counts per split,
-    a short last split, batched), everything else on the register-transposing kernels."""
+    chunks and M >= 2048 run on the transposed-read kernel (gemm_tn_tr_kernel: 256-, 128- and 64-wide b tiles, odd and even chunk
+    counts per split, a short last split), everything else on gemm_tn_x3_kernel<128 | 64>: here (8192, 128, 64), the two shapes with
+    M % 32 != 0, every `rows = M - 100` call and every batched call (fp32 rows, batched, stay off the transposed-read kernel).  No
+    shape of this test reaches gemm_tn_x3_256_kernel; tests/tn_routes.py states the route of a shape, tests/test_tn_routes_gpu.py runs
+    each route per element against float64."""
     ops = _ops()
     g = torch.Generator().manual_seed(M + KA)
     wide = torch.randn(M, KA + KB + 8, generator=g).to(cuda)
@@ -1562,7 +1567,8 @@ def test_bf16_map_operators(cuda):
         assert _rel(c, xa16.double() @ wc.double()) < 2e-5        # the product takes the STORED values
     feat16 = ops.gemm_act(y16, wc, sc, sh, ops.ACT_LEAKY, 0.2, out_bf16=True)[0]
 
-    # pooling / weight gradients with bf16 rows as A (lpd_gemm_tn a_bf16: 128-wide, 64-wide and 256 x 256 tiles, batched)
+    # pooling / weight gradients with bf16 rows as A (lpd_gemm_tn a_bf16).  M = 4224, KA = 1024: gemm_tn_tr_kernel<true, 64 | 128 | 256>;
+    # rows = M - 100 is no multiple of 32: gemm_tn_x3_kernel<64 | 128, true>.  (tests/tn_routes.py states the routes.)
     for KB in (64, 128, 512):
         Bm = torch.randn(M, KB, generator=g).to(cuda)
         got = ops.gemm_tn(feat16, Bm)
@@ -1572,7 +1578,7 @@ def test_bf16_map_operators(cuda):
     M2 = 16384
     big16 = torch.randn(M2, 1024, generator=g).to(cuda).to(bf)
     Bm = torch.randn(M2, 512, generator=g).to(cuda)
-    assert _rel(ops.gemm_tn(big16, Bm), big16.double().t() @ Bm.double()) < 2e-5        # 256 x 256 tiles
+    assert _rel(ops.gemm_tn(big16, Bm), big16.double().t() @ Bm.double()) < 2e-5        # gemm_tn_tr_kernel<true, 256>, not gemm_tn_x3_256_kernel
     A3, B3 = big16.view(4, 4096, 1024), Bm[:, :64].contiguous().view(4, 4096, 64)
     assert _rel(ops.gemm_tn(A3, B3), torch.einsum("bma,bmc->bac", A3.double(), B3.double())) < 2e-5
 
