@@ -1000,6 +1000,68 @@ int lpd_map_insert(const float* points, int ld, int rows, const int32_t* offsets
 int lpd_map_rehash(const long long* keys_in, const long long* acc_in, long long capacity_in, long long* keys, long long* acc,
                    long long capacity, long long* info, void* stream);
 
+/*
+ * Localisation against the drive map (csrc/lpd_localize.hip; arithmetic in csrc/lpd_loc_math.h): the read side of the hash table that
+ * lpd_map_insert fills, and a trimmed point-to-plane ICP of whole posed scans against it -- how a second lap or session is localised
+ * against the map of the first.  This comment is the specification, and lpd_loc_math.h settles every detail it leaves open; the world
+ * row, cell, key, slot, probe count and cell mean are lpd_map_math.h's, the moments lpd_feat_math.h's, the normal, distance, decisions,
+ * quantised row, 29 sums, LDL^T and pose update lpd_icp_math.h's.  No read-back; every call only enqueues.
+ *
+ * Lookup (both calls; lpd_loc_find).  A key is looked up from lpd_map_slot(key, capacity) on, with wrap-around, for at most
+ * lpd_map_probes(capacity) probes: found at the first slot that holds it, absent at the first empty slot or when the probes run out.
+ * Keys are never removed, so the answer does not depend on which slot a key landed in.  A neighbour cell with an index outside
+ * [-2^20, 2^20) on an axis is absent without a lookup; a found slot with m <= 0 is absent.  The table is READ ONLY here: no insert
+ * into it while a call is in flight, and a table that lost rows (its info[2] > 0) is unspecified, as before.
+ *
+ * lpd_map_surface.  surf [capacity][8] fp32, 16-byte aligned, one 32-byte row a slot = (cx, cy, cz, nx, ny, nz, flatness, cells used);
+ * the row of an empty slot is all zeros.  One thread per slot.  For an occupied slot: c = lpd_map_mean of its three sums; the
+ * (2 reach + 1)^3 cells around it are visited in ascending dz, dy, dx (ascending key; the cell itself is one of them), reach 1 or 2;
+ * for every present one d = c_j - c in fp32 goes into lpd_feat_add, k counts them.  k < min_cells (4 .. (2 reach + 1)^3): normal
+ * (0, 0, 0), flatness 0; else (normal, flatness) = lpd_icp_normal(moments, k).  An occupied slot with m <= 0 (no insert makes one) gets
+ * (NaN, NaN, NaN, 0, 0, 0, 0, 0): never the nearest of anything.  info [2] int64, ADDED to: slots written with a normal, occupied slots
+ * written without one.  The values per key do not depend on slot placement, only their position in surf does.
+ *
+ * lpd_map_localize.  points / ld / rows / offsets / S / scan0 / scan1 / origin / inv_cell as lpd_map_insert takes them.
+ *   keys, surf, capacity   the table and its lpd_map_surface rows (acc is not needed)
+ *   pose       [S][12] float64, IN and OUT: only the scans scan0 .. scan1-1 are touched
+ *   dmax       HOST array of iters + 1 fp32, each finite, > 0, <= 16;  0 <= iters <= 64;  min_inliers >= 6;  max_flat in (0, 1]
+ *   sums       [iters+1][S][32] int64, cleared by the call; the layout of lpd_icp_pairs per (pass, scan)
+ *   cell       [rows] int64 or NULL: the LAST pass's corresponding cell key of every row of offsets[scan0] .. offsets[scan1]-1, or -1
+ *   info       [S][4] int32, rows scan0 .. scan1-1: (1 for a valid scan else -1, steps applied, steps refused, correspondences of the
+ *              last pass)
+ *   ws         lpd_map_localize_workspace_bytes(S, iters) bytes, 16-byte aligned
+ * A scan is VALID iff its pose is finite, 0 <= offsets[i] <= offsets[i+1] <= rows and it has at most 2^20 rows (2^20 terms of at most
+ * 2^40 stay inside an int64).  An invalid scan's pose is left bit for bit, its sums are 0, its rows' cell is -1 and its rows are never
+ * read.  The rows are walked as lpd_map_insert walks them (rule 5 there): nothing is read unless 0 <= offsets[scan0] <= offsets[scan1]
+ * <= rows, and the rows of a chunk whose part of the offsets table is not one have no correspondence (cell -1).
+ * Each pass s runs at the pose that pass s - 1 left:
+ *  1 Centre.   Fixed once at entry: g = t_in - origin in float64, g32 = g rounded to fp32.  Residuals are formed around the scan, not
+ *              around the map's origin: a lever arm of kilometres would hit the 2^20 clamp of lpd_icp_quant and ruin the conditioning.
+ *  2 World row. Exactly the insert's: lpd_map_rel(pose_i, origin) rounded to fp32 once, w_c = lpd_drive_coord(...), so a scan at its
+ *              true pose reads exactly the cells it was inserted into; q_c = lpd_map_index(w_c, inv_cell).  A row without a cell has
+ *              no correspondence.
+ *  3 Correspondence.  Candidates: the 27 cells q + (dx, dy, dz), each offset in -1 .. 1, in ascending dz, dy, dx.  For every present
+ *              one d2 = lpd_icp_d2(c, w), c its surf centroid; the running minimum is lpd_icp_nearer (strict: ties go to the lowest
+ *              key; a d2 that is not finite never wins).  The winner is the correspondence iff lpd_icp_within(d2, dmax_s), its normal is
+ *              not (0, 0, 0) and its flatness <= max_flat.  Only this outcome is specified.  With dmax <= cell no nearer centroid lies
+ *              outside the 27 cells; the call does not enforce that.
+ *  4 Row.      p = w - g32 and q = c - g32, one fp32 subtraction each; a row with any |p_c| > 512 has no correspondence; then
+ *              lpd_icp_row(p, q, n) and lpd_icp_terms, summed in int64: exact in any order.
+ *  5 Step.     Passes 0 .. iters-1, float64: lpd_icp_solve's sequence with the rotation about the centre -- T = (t - origin) - g,
+ *              (R | T) updated by lpd_icp_update, t = (T' + g) + origin -- refused, the pose left bit for bit, under lpd_icp_solve's
+ *              conditions (lpd_loc_step).
+ * Integer atomics only: the same bits in every launch, at every capacity and for every slot placement.
+ */
+#define LPD_LOC_SURF 8                     /* floats of a surf row */
+#define LPD_LOC_MAX_ITERS 64
+#define LPD_LOC_MAX_SCAN_ROWS 1048576      /* 2^20 rows a scan */
+int lpd_map_surface(const long long* keys, const long long* acc, long long capacity, int reach, int min_cells, float* surf, long long* info,
+                    void* stream);
+long long lpd_map_localize_workspace_bytes(int S, int iters);
+int lpd_map_localize(const float* points, int ld, int rows, const int32_t* offsets, int S, int scan0, int scan1, const double* origin,
+                     float inv_cell, const long long* keys, const float* surf, long long capacity, const float* dmax, int iters,
+                     int min_inliers, float max_flat, double* pose, int32_t* info, long long* sums, long long* cell, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

@@ -15,12 +15,23 @@ count is a quality measure of a loop closure that needs no ground truth: it fall
 
 The sums are integers (units of 2^-16 m), so the map does not depend on the order in which threads, batches or drives arrive; it equals
 the numpy restatement (tests/map_ref.py) bit for bit.  No CPU fallback.
+
+The map is what a second lap or session is localised against (csrc/lpd_localize.hip): lap one closed, corrected and mapped as above;
+lap two's odometry poses in; localised poses out; lap two inserted into the same map.
+
+    loc = mapping.localize_scans(m, points2, lengths2, odometry2)              # Localization: trimmed point-to-plane ICP against the cells
+    loc.poses, loc.inliers, loc.rms                                            # [S2, 12] float64, share of rows with a cell, metres
+    m.insert(points2, lengths2, loc.poses)                                     # ... and drive.submaps_from_drive(points2, lengths2, loc.poses)
+
+Every sum of the ICP is an integer as well, and the lookup of a cell does not depend on the slot it landed in: the localised poses are
+the same bits in every launch and at every table size, and equal tests/loc_ref.py bit for bit.
 """
 import numpy as np
 import torch
 
 from . import drive, ops, submap
 from ._lib import LpdHipError
+from .verify import _Frozen
 
 # The first capacity: the smallest power of two >= rows / 2 of the first insert -- a cell for every FOUR rows at a load of one half --
 # and at least 2^16 slots (2.5 MiB).  tools/map_bench.py counted 5.4 .. 262 rows per occupied cell on the two bench drives with rows in
@@ -124,6 +135,7 @@ class VoxelMap:
                 raise ValueError(f"{what}: capacity={capacity} is not a power of two in 16 .. 2^36")
         self._first_capacity = capacity
         self.keys = self.acc = self.info = None
+        self._surface = None      # (reach, min_cells, surf, info): slot-indexed, so every insert and every growth drops it
         self.grown = 0      # doublings so far
 
     @property
@@ -145,6 +157,7 @@ class VoxelMap:
                 if int(info[2]):
                     continue
             self.keys, self.acc, self.info = keys, acc, info
+            self._surface = None
             self.grown += 1
             return
         raise LpdHipError(f"VoxelMap: the table cannot grow beyond {self.capacity} slots")
@@ -180,6 +193,7 @@ class VoxelMap:
                     self.origin = p[torch.argmax(finite.to(torch.int32))][[3, 7, 11]].contiguous()      # the first finite pose; no wait
                 if n == 0:
                     return self
+                self._surface = None
                 offsets = drive._scan_offsets(lengths, self.device)
                 if self.keys is None:
                     cap = self._first_capacity
@@ -226,6 +240,154 @@ class VoxelMap:
             raise ValueError("VoxelMap.cells: nothing was inserted")
         with torch.no_grad():
             return extract_cells(self.keys, self.acc, self.origin, self.cell)
+
+    def surface(self, reach=1, min_cells=5):
+        """The read side of the table (lpd_map_surface) -> surf [capacity, 8] fp32 on the device, one row a SLOT: (cx, cy, cz, nx, ny,
+        nz, flatness, cells used), all zeros for an empty slot.  The normal of a cell comes from the centroids of the present cells among
+        the (2 reach + 1)^3 around it (reach 1 or 2), (0, 0, 0) with fewer than min_cells of them.  Made once and kept; every insert and
+        every growth of the table drops it, because it is indexed by slot.  Nothing is read back."""
+        what = "VoxelMap.surface"
+        reach, min_cells = ops.map_surface_params(what, reach, min_cells)
+        if self.keys is None:
+            raise ValueError(f"{what}: nothing was inserted")
+        if self._surface is None or self._surface[:2] != (reach, min_cells):
+            with torch.cuda.device(self.device), torch.no_grad():
+                self._surface = (reach, min_cells) + ops.map_surface(self.keys, self.acc, reach, min_cells)
+        return self._surface[2]
+
+    def surface_cells(self, reach=1, min_cells=5):
+        """-> SurfaceCells in ascending key order, the order of cells(): normals [M, 3] fp32, flatness [M] fp32, used [M] int64 (plain
+        torch: a mask, a sort, a gather)"""
+        surf = self.surface(reach, min_cells)
+        with torch.no_grad():
+            live = self.keys >= 0
+            k, order = torch.sort(self.keys[live])
+            s = surf[live][order]
+            return SurfaceCells(s[:, 3:6].contiguous(), s[:, 6].contiguous(), s[:, 7].to(torch.int64), k, s[:, :3].contiguous())
+
+
+class SurfaceCells:
+    """What VoxelMap.surface_cells returns, on the device, in ascending key order: normals [M, 3] fp32 (unit, or (0, 0, 0)), flatness [M]
+    fp32 = l3 / l2 of the centroids' covariance, used [M] int64 = the cells the normal was made from, keys [M] int64, points [M, 3] fp32."""
+    __slots__ = ("normals", "flatness", "used", "keys", "points")
+
+    def __init__(self, normals, flatness, used, keys, points):
+        self.normals, self.flatness, self.used, self.keys, self.points = normals, flatness, used, keys, points
+
+    def __len__(self):
+        return int(self.keys.shape[0])
+
+
+class LocalizeSearch(_Frozen):
+    """The search of localize_scans, validated and frozen.  iters: steps (0 .. 64); dmax: the trimming distance in metres -- None:
+    min(cell, 16) for the first iters // 2 + 1 passes and half of that afterwards, so that no nearer centroid lies outside the 27 cells
+    searched; one number; or a sequence of iters + 1 numbers, one a pass; min_inliers: a step with fewer correspondences is refused
+    (>= 6); max_flat: a cell whose centroids' l3 / l2 exceeds it gives no correspondence, in (0, 1]; reach, min_cells: VoxelMap.surface's."""
+    __slots__ = ("iters", "dmax", "min_inliers", "max_flat", "reach", "min_cells")
+
+    def __init__(self, iters=8, dmax=None, min_inliers=50, max_flat=0.3, reach=1, min_cells=5):
+        what = "LocalizeSearch"
+        self._set("iters", self._whole(iters, "iters", 0, ops.LOC_MAX_ITERS))
+        self._set("min_inliers", self._whole(min_inliers, "min_inliers", ops.LOC_MIN_INLIERS, (1 << 31) - 1))
+        if isinstance(max_flat, bool) or not isinstance(max_flat, (int, float, np.integer, np.floating)) or not 0.0 < float(max_flat) <= 1.0:
+            raise ValueError(f"{what}: max_flat={max_flat!r} outside (0, 1]")
+        self._set("max_flat", float(max_flat))
+        try:
+            reach, min_cells = ops.map_surface_params(what, reach, min_cells)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+        self._set("reach", reach)
+        self._set("min_cells", min_cells)
+        if dmax is not None:
+            if not isinstance(dmax, (list, tuple, np.ndarray)):
+                dmax = (dmax,) * (self.iters + 1)
+            if len(dmax) != self.iters + 1:
+                raise ValueError(f"{what}: dmax holds {len(dmax)} entries; iters + 1 = {self.iters + 1}")
+            for i, v in enumerate(dmax):
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                    raise ValueError(f"{what}: dmax[{i}]={v!r} (a number)")
+            dmax = tuple(float(v) for v in dmax)
+            ops.map_localize_dmax(what, dmax)
+        self._set("dmax", dmax)
+
+    def schedule(self, cell):
+        """the iters + 1 distances of lpd_map_localize on a map of `cell` metres"""
+        if self.dmax is not None:
+            return self.dmax
+        wide = min(float(cell), ops.LOC_MAX_DMAX)
+        n_wide = min(self.iters // 2 + 1, self.iters + 1)
+        return (wide,) * n_wide + (0.5 * wide,) * (self.iters + 1 - n_wide)
+
+
+class Localization:
+    """What localize_scans returns, on the device, one entry a scan: poses [S, 12] float64 (scans that were not asked for, and invalid
+    ones, keep their input pose bit for bit); valid [S] bool (False: not asked for, a pose that is not finite, more than 2^20 rows);
+    steps, refused [S] int32 = the steps applied and refused; inliers [S] float64 = the last pass's correspondences over the scan's
+    length (0 for an empty scan); rms [S] float64 metres = sqrt(sum ri^2 / m) / 1024 of the last pass, 0 where m = 0; sums
+    [iters + 1, S, 32] int64 = every pass's sums; cells [rows] int64 or None = the last pass's cell key of every row, -1 without a
+    correspondence."""
+    __slots__ = ("poses", "valid", "steps", "refused", "inliers", "rms", "sums", "cells")
+
+    def __init__(self, poses, valid, steps, refused, inliers, rms, sums, cells):
+        self.poses, self.valid, self.steps, self.refused, self.inliers, self.rms, self.sums, self.cells = (poses, valid, steps, refused, inliers,
+                                                                                                         rms, sums, cells)
+
+    def __len__(self):
+        return int(self.poses.shape[0])
+
+
+def _scan_range(what, scans, S):
+    if scans is None:
+        return 0, S
+    a, b = (scans.start, scans.stop) if isinstance(scans, range) else (int(v) for v in scans)
+    if isinstance(scans, range) and scans.step != 1:
+        raise ValueError(f"{what}: scans must be a contiguous range")
+    if not 0 <= a <= b <= S:
+        raise ValueError(f"{what}: scans {a} .. {b} outside 0 .. {S}")
+    return a, b
+
+
+def localize_scans(vmap, points, lengths, poses, search=LocalizeSearch(), scans=None, want_cells=False):
+    """Posed scans localised against a VoxelMap: trimmed point-to-plane ICP of every scan, as a whole, against the centroids and normals
+    of the map's cells (lpd_map_localize) -> Localization.  points / lengths / poses / scans as VoxelMap.insert takes them, each scan in
+    its own sensor frame and `poses` the start -- odometry, or the last fix carried forward; a start within about a cell and a few
+    degrees converges.  The result's poses go straight into drive.submaps_from_drive, VoxelMap.insert and
+    correct_scan_poses.  Judge a scan by `inliers`: a scan at the right place keeps a third or more of its rows, one that is lost a few
+    per cent.  Nothing waits for the device."""
+    what = "localize_scans"
+    if not isinstance(vmap, VoxelMap):
+        raise TypeError(f"{what}: vmap must be a VoxelMap, got {type(vmap).__name__}")
+    if not isinstance(search, LocalizeSearch):
+        raise TypeError(f"{what}: search must be a LocalizeSearch, got {type(search).__name__}")
+    if vmap.keys is None:
+        raise ValueError(f"{what}: nothing was inserted into the map")
+    pts, lengths = drive._drive_input(points, lengths)
+    with torch.no_grad():
+        p = drive._poses(poses, vmap.device, what)
+        lengths = drive._lengths(lengths, p.shape[0], what)
+        S = p.shape[0]
+        a, b = _scan_range(what, scans, S)
+        rows = submap._device_rows(pts, vmap.device)
+        if rows.device != vmap.device or p.device != vmap.device:
+            raise ValueError(f"{what}: points on {rows.device}, poses on {p.device}, the map on {vmap.device}")
+        dev = vmap.device
+        with torch.cuda.device(dev):
+            n = int(lengths[a:b].sum())
+            if n == 0 or rows.shape[0] == 0:      # nothing to read: every scan keeps its pose
+                zero = torch.zeros((S,), dtype=torch.int32, device=dev)
+                return Localization(p.clone(), torch.zeros((S,), dtype=torch.bool, device=dev), zero, zero.clone(),
+                                    torch.zeros((S,), dtype=torch.float64, device=dev), torch.zeros((S,), dtype=torch.float64, device=dev),
+                                    torch.zeros((search.iters + 1, S, ops.LOC_SUMS), dtype=torch.int64, device=dev),
+                                    torch.full((rows.shape[0],), -1, dtype=torch.int64, device=dev) if want_cells else None)
+            offsets = drive._scan_offsets(lengths, dev)
+            surf = vmap.surface(search.reach, search.min_cells)
+            pose, info, sums, cells = ops.map_localize(rows, offsets, p, vmap.origin, vmap.inv_cell, vmap.keys, surf, search.schedule(vmap.cell),
+                                                       search.min_inliers, search.max_flat, a, b, want_cells)
+            m = sums[-1, :, 0].to(torch.float64)
+            n_rows = torch.from_numpy(np.asarray(lengths, dtype=np.float64)).to(dev)
+            inliers = torch.where(n_rows > 0, info[:, 3].to(torch.float64) / n_rows.clamp(min=1.0), torch.zeros_like(n_rows))
+            rms = torch.where(m > 0, torch.sqrt(sums[-1, :, 28].to(torch.float64) / m.clamp(min=1.0)) / 1024.0, torch.zeros_like(m))
+    return Localization(pose, info[:, 0] == 1, info[:, 1].contiguous(), info[:, 2].contiguous(), inliers, rms, sums, cells)
 
 
 def build_map(points, lengths, poses, cell=0.2, origin=None, capacity=None, device=None):

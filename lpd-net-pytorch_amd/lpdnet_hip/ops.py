@@ -1673,6 +1673,125 @@ def map_rehash(keys_in, acc_in, keys, acc, info):
     _call("map_rehash", _lib.load().lpd_map_rehash, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(keys), _ptr(acc), cap, _ptr(info), _stream())
 
 
+# localisation against the drive map (csrc/lpd_localize.hip)
+LOC_SURF, LOC_MAX_ITERS, LOC_MAX_SCAN_ROWS = _defines("LOC", "SURF", "MAX_ITERS", "MAX_SCAN_ROWS")
+LOC_MIN_CELLS = 4
+LOC_SUMS = _lib.DEFINES["LPD_ICP_SUMS"]
+LOC_MIN_INLIERS = _lib.DEFINES["LPD_ICP_MIN_INLIERS"]
+LOC_MAX_DMAX = 16.0      # csrc/lpd_icp_math.h
+
+
+def map_surface_params(what, reach, min_cells):
+    """reach (1 or 2) and min_cells (4 .. (2 reach + 1)^3) of lpd_map_surface, checked on the host -> (reach, min_cells)"""
+    for v, name in ((reach, "reach"), (min_cells, "min_cells")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"{what}: {name} must be an integer, got {type(v).__name__}")
+    reach, min_cells = int(reach), int(min_cells)
+    if reach not in (1, 2):
+        raise ValueError(f"{what}: reach={reach} (1 or 2)")
+    if not LOC_MIN_CELLS <= min_cells <= (2 * reach + 1) ** 3:
+        raise ValueError(f"{what}: min_cells={min_cells} outside {LOC_MIN_CELLS} .. {(2 * reach + 1) ** 3}")
+    return reach, min_cells
+
+
+def map_surface(keys, acc, reach=1, min_cells=5, info=None):
+    """The read side of a voxel hash table (lpd_map_surface; definition in include/lpd_hip.h): keys [capacity] int64 and acc
+    [capacity, 4] int64 as map_insert left them -> (surf [capacity, 8] fp32 = (cx, cy, cz, nx, ny, nz, flatness, cells used) a slot,
+    all zeros for an empty one; info [2] int64 = slots with a normal, occupied slots without one; a given info is added to).  Nothing is
+    read back."""
+    what = "map_surface"
+    reach, min_cells = map_surface_params(what, reach, min_cells)
+    _req(keys, "keys", torch.int64)
+    _req(acc, "acc", torch.int64)
+    if keys is None or acc is None:
+        raise TypeError(f"{what}: keys and acc are tensors")
+    cap = keys.shape[0] if keys.dim() == 1 else 0
+    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
+    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous() or acc.device != keys.device:
+        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor on {keys.device}, got {tuple(acc.shape)}")
+    if info is None:
+        info = _zeros((2,), torch.int64, keys.device)
+    else:
+        _req(info, "info", torch.int64)
+        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != keys.device:
+            raise ValueError(f"{what}: info must be a contiguous [2] int64 tensor on {keys.device}")
+    surf = torch.empty((cap, LOC_SURF), dtype=torch.float32, device=keys.device)
+    _call("map_surface", _lib.load().lpd_map_surface, _ptr(keys), _ptr(acc), cap, reach, min_cells, _ptr(surf), _ptr(info), _stream())
+    return surf, info
+
+
+def map_localize_dmax(what, dmax):
+    """the HOST array of iters + 1 fp32 distances of lpd_map_localize from a sequence -> (array, iters)"""
+    try:
+        vals = [float(v) for v in dmax]
+    except TypeError:
+        raise TypeError(f"{what}: dmax must be a sequence of iters + 1 distances") from None
+    iters = len(vals) - 1
+    if not 0 <= iters <= LOC_MAX_ITERS:
+        raise ValueError(f"{what}: dmax holds {iters + 1} entries; iters + 1 lies in 1 .. {LOC_MAX_ITERS + 1}")
+    arr = (ctypes.c_float * (iters + 1))(*vals)
+    for s, (v, r) in enumerate(zip(vals, arr)):
+        if not (0.0 < v <= LOC_MAX_DMAX and 0.0 < float(r) <= LOC_MAX_DMAX):      # false for NaN as well; before and after the rounding
+            raise ValueError(f"{what}: dmax[{s}]={v!r} (finite, > 0, <= {LOC_MAX_DMAX})")
+    return arr, iters
+
+
+def map_localize(points, offsets, poses, origin, inv_cell, keys, surf, dmax, min_inliers=50, max_flat=0.3, scan0=0, scan1=None,
+                 want_cells=False):
+    """Trimmed point-to-plane ICP of the scans scan0 .. scan1-1 against a voxel map (lpd_map_localize; definition in include/lpd_hip.h):
+    points [rows, >=3] fp32 with contiguous rows, offsets [S+1] int32, poses [S, 12] float64 = the start (not written: the result is a
+    new tensor) and origin [3] float64 on the device; inv_cell = map_inv_cell(cell); keys [capacity] int64 and surf [capacity, 8] fp32
+    (map_surface) the map; dmax: iters + 1 distances in metres on the host, one a pass; min_inliers >= 6; 0 < max_flat <= 1.
+    -> (poses [S, 12] float64, info [S, 4] int32 = (1 | -1, steps applied, steps refused, correspondences of the last pass; rows
+    outside the scans are 0), sums [iters + 1, S, 32] int64, cells [rows] int64 or None = the last pass's cell key of every row, -1
+    without a correspondence).  Nothing is read back."""
+    what = "map_localize"
+    _req(points, "points")
+    _req(origin, "origin", torch.float64)
+    _req(keys, "keys", torch.int64)
+    _req(surf, "surf")
+    poses, S = _drive_poses(what, poses)
+    if points is None or origin is None or keys is None or surf is None:
+        raise TypeError(f"{what}: points, origin, keys and surf are tensors")
+    ld = _scan_points(what, points)
+    offsets = _drive_offsets(what, offsets, S)
+    if tuple(origin.shape) != (3,):
+        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
+    cap = keys.shape[0] if keys.dim() == 1 else 0
+    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
+    if tuple(surf.shape) != (cap, LOC_SURF) or not surf.is_contiguous() or surf.data_ptr() % 16:
+        raise ValueError(f"{what}: surf must be a contiguous, 16-byte aligned [capacity, {LOC_SURF}] = ({cap}, {LOC_SURF}) tensor, got {tuple(surf.shape)}")
+    if len({points.device, offsets.device, poses.device, origin.device, keys.device, surf.device}) != 1:
+        raise ValueError(f"{what}: points, offsets, poses, origin and the map must be on one device")
+    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
+    if not 0 <= scan0 < scan1 <= S:
+        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
+    inv_cell = float(inv_cell)
+    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    dm, iters = map_localize_dmax(what, dmax)
+    if isinstance(min_inliers, bool) or not isinstance(min_inliers, numbers.Integral) or not LOC_MIN_INLIERS <= int(min_inliers) < 1 << 31:
+        raise ValueError(f"{what}: min_inliers={min_inliers!r} (an integer >= {LOC_MIN_INLIERS})")
+    if isinstance(max_flat, bool) or not isinstance(max_flat, numbers.Real) or not 0.0 < float(max_flat) <= 1.0:
+        raise ValueError(f"{what}: max_flat={max_flat!r} outside (0, 1]")
+    max_flat32 = ctypes.c_float(float(max_flat)).value
+    if not 0.0 < max_flat32 <= 1.0:
+        raise ValueError(f"{what}: max_flat={max_flat!r} rounds to fp32 outside (0, 1]")
+    lib = _lib.load()
+    dev = points.device
+    pose = poses.clone()
+    info = torch.zeros((S, 4), dtype=torch.int32, device=dev)
+    sums = torch.empty((iters + 1, S, LOC_SUMS), dtype=torch.int64, device=dev)
+    cells = torch.full((points.shape[0],), -1, dtype=torch.int64, device=dev) if want_cells else None
+    ws = torch.empty((max(int(lib.lpd_map_localize_workspace_bytes(S, iters)), 16),), dtype=torch.uint8, device=dev)
+    _call("map_localize", lib.lpd_map_localize, _ptr(points), ld, points.shape[0], _ptr(offsets), S, scan0, scan1, _ptr(origin.contiguous()),
+          inv_cell, _ptr(keys), _ptr(surf), cap, dm, iters, int(min_inliers), max_flat32, _ptr(pose), _ptr(info), _ptr(sums), _ptr(cells),
+          _ptr(ws), _stream())
+    return pose, info, sums, cells
+
+
 # ------------------------------------------------------------------------------------------------
 # geometric verification of retrieved places (csrc/lpd_align.hip)
 # ------------------------------------------------------------------------------------------------
