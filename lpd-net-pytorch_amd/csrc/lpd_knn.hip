@@ -704,7 +704,13 @@ void knn3_kernel(const float* __restrict__ xp, const float* __restrict__ xx, int
 //     the k-th-best thresholds are tight from the second tile on (a pre-sorted centroid-distance order visited the same
 //     ~40 of 128 tiles and cost a sort kernel);
 //   * skips a tile, before loading or multiplying anything, when no query of the wave can gain from it
-//     (ub[i][T] < threshold_i for all i): one LDS read, a compare and a wave vote.
+//     (ub[i][T] < threshold_i for all i): one LDS read, a compare and a wave vote;
+//   * 64 channels, N <= 4096, k <= 20, one wave per tile (knn7_kernel<..., SORTED>): the bounds are the low-precision pass's table,
+//     whole in LDS before the first visit, so the wave sorts the cloud's tiles by their best bound once (two keys per lane, a
+//     bitonic network in registers), visits its own tile and then the tiles in that order, and ENDS the walk at the first tile whose
+//     best bound is below the smallest threshold of its queries.  The Z-curve walk looked at all 128 tiles for 23 visits; this
+//     one looks at 26.  Per wave at 32 x 4096 x 64 (tools/knn7_stats.py): walk 66 k -> 21 k cycles, wave 255 k -> 209 k; kernel inside
+//     the forward 281 -> 256 us (profiles/knn_sorted_walk.txt).  LPD_DEBUG=no-knn-sorted: the Z-curve walk.
 // Exactness: a tile is skipped only if every pd in it is provably below the thresholds (the slack covers the rounding
 // of the fp32 pd evaluation), so the admitted SET equals that of the full scan; exact value ties are ranked by index:
 // in the short lists (k <= 20) by the keys of the batched drain (knn_merge_batch), in the 64-entry lists through the interval
@@ -735,6 +741,68 @@ template <int CP, int KMAX, bool ONFLY> struct Knn7Cfg {
     static constexpr int QOFF = TBYTES;      // byte offset of the queue inside the wave's region
     static constexpr int WAVES_PER_SIMD = KMAX > 20 ? (CP == 2 ? 2 : 1) : (CP == 2 ? 4 : 2);
 };
+
+// ---- walk in bound order (knn7_kernel<..., SORTED>): the score of a tile and the sort of the cloud's tiles by it ----
+// A table entry is the bf16 bit pattern of a bound <= 0, or 0x7f80 ("visit").  Its IMAGE is the 16-bit number
+//     img(u) = u            for u >= 0x8000   (-0, the finite negatives, -inf: sign-magnitude, a larger pattern is a smaller float)
+//            = 0x7fff - u   for u <  0x8000   (+0 -> 0x7fff, 0x7f80 -> 0x007f)
+// whose UNSIGNED ASCENDING order is the DESCENDING float order of every pattern the table holds:
+//     0x7f80 (image 0x007f)  <  +0 (0x7fff)  <  -0 (0x8000)  <  -tiny (0x8001)  < ... <  -huge (0xff7f)  <  -inf (0xff80).
+// (+0 and -0 are equal as floats; the image puts +0 first, which is a descending order still.)  img is its own inverse.  The score
+// of a tile is the smallest image among the wave's 32 entries for it, i.e. the LARGEST bound any of its queries has for the tile.
+// tests/test_knn_sorted_walk_cpu.py states the image, the key and the stop rule in numpy.
+typedef unsigned short knn_u16x2 __attribute__((ext_vector_type(2)));
+__host__ __device__ inline uint32_t knn7_score_img(uint32_t u) { return (u & 0x8000u) ? u : 0x7fffu - u; }      // one 16-bit pattern
+__device__ __forceinline__ float knn7_score_bound(uint32_t img) { return __uint_as_float(knn7_score_img(img) << 16); }
+__device__ __forceinline__ knn_u16x2 knn7_score_img2(uint32_t w)      // both halves of a word (0x7fff - u == 0x7fff ^ u below 0x8000)
+{
+    const uint32_t pos = (~w >> 15) & 0x00010001u;      // 1 in each half whose sign bit is clear
+    return __builtin_bit_cast(knn_u16x2, w ^ ((pos << 15) - pos));
+}
+// smallest image of the 32 entries of table row T (64 bytes)
+__device__ __forceinline__ uint32_t knn7_tile_score(const uint16_t* row)
+{
+    const uint4* p = reinterpret_cast<const uint4*>(row);
+    knn_u16x2 m = {0xffff, 0xffff};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint4 v = p[i];
+        m = __builtin_elementwise_min(m, __builtin_elementwise_min(__builtin_elementwise_min(knn7_score_img2(v.x), knn7_score_img2(v.y)),
+                                                                    __builtin_elementwise_min(knn7_score_img2(v.z), knn7_score_img2(v.w))));
+    }
+    return min((uint32_t)m.x, (uint32_t)m.y);
+}
+// Sort 128 keys, two per lane, ascending: a bitonic network over the elements e = r * 64 + lane (r: register).  Afterwards walk
+// position p is register p >> 6 of lane p & 63.  Exchanges at distance 1 and 2 are DPP quad permutes, 4 .. 32 lane shuffles, 64 is the
+// lane's own pair: 27 cross-lane steps of two registers, once per wave.
+__device__ __forceinline__ uint32_t knn7_xor_lane(uint32_t v, int j)
+{
+    if (j == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);      // quad_perm [1, 0, 3, 2]
+    if (j == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);      // quad_perm [2, 3, 0, 1]
+    return (uint32_t)__shfl_xor((int)v, j, 64);
+}
+__device__ __forceinline__ void knn7_sort128(uint32_t& k0, uint32_t& k1, int lane)
+{
+#pragma unroll
+    for (int kk = 2; kk <= 128; kk <<= 1) {             // merge sorted runs of kk / 2 into runs of kk
+#pragma unroll
+        for (int j = kk >> 1; j >= 1; j >>= 1) {
+            if (j == 64) {                              // kk == 128: one ascending run
+                const uint32_t lo = min(k0, k1), hi = max(k0, k1);
+                k0 = lo;
+                k1 = hi;
+                continue;
+            }
+            const uint32_t p0 = knn7_xor_lane(k0, j), p1 = knn7_xor_lane(k1, j);
+            const bool lower = (lane & j) == 0;
+            // run of element e ascends where bit kk of e is clear: a lane bit below 64, the register for kk == 64, everywhere for 128
+            const bool asc0 = kk < 64 ? (lane & kk) == 0 : true;
+            const bool asc1 = kk < 64 ? (lane & kk) == 0 : kk == 128;
+            k0 = lower == asc0 ? min(k0, p0) : max(k0, p0);
+            k1 = lower == asc1 ? min(k1, p1) : max(k1, p1);
+        }
+    }
+}
 
 // Merge of the two half-lists of every query (lanes l and l + 32 hold disjoint candidate subsets, each sorted by (value descending,
 // index ascending)) without LDS: a bitonic merge on registers.  Stage 1 (half-cleaner against the partner's REVERSED list, read by
@@ -1419,7 +1487,9 @@ __device__ __forceinline__ void knn7_store_idx16(uint16_t* __restrict__ idx16, s
 // on its first tile -- letting wave 0 take the query tile alone first, the others starting from its bound, changed nothing (16 clouds
 // 444 us against 421) -- but because a drain lasts as long as its fullest lane, and a wave that sees a quarter of the candidates has
 // the same maximum for a quarter of the average.
-template <int CP, int KMAX, int WAVES, bool ONFLY, bool FULLT = false, int SPLIT = 1>
+// SORTED (the table in LDS, short lists, one wave per tile): the walk visits the tiles in the order of their scores instead of along
+// the Z-curve and ends at the first tile that no query can gain from -- see "walk in bound order" below.
+template <int CP, int KMAX, int WAVES, bool ONFLY, bool FULLT = false, int SPLIT = 1, bool SORTED = false>
 __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : Knn7Cfg<CP, KMAX, ONFLY>::WAVES_PER_SIMD)) void knn7_kernel(const float* __restrict__ xp, const float* __restrict__ xx,
                                                              const float* __restrict__ cenp, const float* __restrict__ cnorm,
                                                              const float* __restrict__ rad, const float* __restrict__ txmax,
@@ -1515,6 +1585,34 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
 
     if constexpr (SPLIT > 1) __syncthreads();      // the shared bound table and the threshold slots are in place
 
+    // ---- walk in bound order: the whole table [nt][32] is in LDS before anything is visited, so the walk is decided once ----
+    //  1. score of tile T: the largest bound any of the wave's 32 queries has for it (knn7_tile_score, as an image that sorts);
+    //  2. key = image << 8 | T, sorted ascending across the wave: best bound first, ties to the lower tile, absent tiles (all ones) last;
+    //     walk position p is ord[p >> 6] of lane p & 63 -- two registers, no LDS (table + queue are the CU's whole 160 KiB at 8 waves);
+    //  3. find_next_sorted reads position after position and ENDS the walk at the first key whose score is below the smallest threshold
+    //     of the wave's real queries (thr_min, reduced in drain()).
+    // The order is free for the short lists: their drain ranks by the 64-bit key (pd, index), so the lists hold the k best keys of the
+    // admitted set whatever order they arrived in, and a tile is still skipped only when no query's bound reaches its threshold.
+    static_assert(!SORTED || (CP == 32 && !ONFLY && SPLIT == 1 && KMAX <= 20), "SORTED: the route of find_next_lds8 with the 64-bit keys");
+    static_assert(!SORTED || KNN7_MAXT <= 128, "SORTED: two keys per lane, the tile in the key's low byte");
+    uint32_t ord0 = 0xffffffffu, ord1 = 0xffffffffu;
+    float thr_min = -INFINITY;                  // smallest thrv of the wave's real queries (wave-uniform); -inf until every list is full
+    if constexpr (SORTED) {
+        if (wave_ok) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the rows below were written by other lanes of this wave
+            if (lane < nt) ord0 = knn7_tile_score(ubt + lane * 32) << 8 | (uint32_t)lane;
+            if (lane + 64 < nt) ord1 = knn7_tile_score(ubt + (lane + 64) * 32) << 8 | (uint32_t)(lane + 64);
+            knn7_sort128(ord0, ord1, lane);
+            // statistics variant: the walk order as sorted keys (-1 beyond nt).  Lane l = h * 32 + col holds positions l and 64 + l, so
+            // row col of the wave carries positions col, 32 + col, 64 + col, 96 + col in o[12 .. 15] (o[0 .. 11] are written at the end)
+            if (dbg && q_ok && k >= 16) {
+                int32_t* o = idx + ((size_t)b * N + q) * k;
+                o[12 + h] = (int)ord0;
+                o[14 + h] = (int)ord1;
+            }
+        }
+    }
+
     float lv[KMAX];
     int li[KMAX];
 #pragma unroll
@@ -1561,7 +1659,8 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
     int stat_tiles = 0, stat_it = 0, stat_adm = 0, stat_drains = 0, stat_fn = 0, stat_pass = 0;   // diagnostics (dbg): visited tiles, sum of the drains' fullest lanes, admitted, drains, bound tests, batches
 
     // visiting order: outwards along the Z-curve, W, W+1, W-1, W+2, ... (the visited tiles always form an interval around
-    // W, which is what makes the one-compare insertion of the 64-entry lists exact)
+    // W, which is what makes the one-compare insertion of the 64-entry lists exact).  SORTED: spos is the position in the sorted order
+    // (find_next_sorted below); its lists are the 64-bit keys, which need no interval.
     int spos = 0;
     int vcount = 0;                        // SPLIT > 1: tiles of the cloud met so far in walk order (dealt round-robin to the waves)
     auto find_next_walk = [&]() -> int {   // next tile in order that some query of the wave can still gain from; -1 at the end
@@ -1684,7 +1783,50 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
     // (The same batching for three coordinates -- centroids and radii of eight walk positions requested together, eight bounds cached
     //  -- made the xyz walk SLOWER, 177 -> 201 us at 32 clouds: its per-tile test is a scalar load and a dozen vector instructions, not a
     //  dependent LDS round trip, and the cached form re-votes eight bounds per call.)
+    // Walk in bound order (SORTED; the Z-curve forms above remain for LPD_DEBUG=no-knn-sorted and for every other route).  Measured on
+    // the Z-curve, find_next_lds8 was a quarter of a wave's life (65 k of 252 k cycles, profiles/knn_batched_drain.txt): it looks at all
+    // 128 tiles of the cloud, eight cached bounds re-voted per call, for 23 visits.  Here a call costs a v_readlane, a scalar compare
+    // and, per position, the SAME per-query test as before: one ds_read_u16 of the query's bound, ub >= thrv, wave vote.
+    // Why the walk may END at the first key with score < thr_min (all as floats; spos = nt, nothing behind it is looked at):
+    //   * keys ascend, so the scores (largest bound of any query for the tile) descend along the walk: score(p') <= score(p), p' > p;
+    //   * a tile's score bounds every query's entry for it: ub[q][T] <= score(T);
+    //   * thresholds never fall (a drain only replaces list entries by better keys), and thr_min <= thrv[q] for every real query;
+    //     a padded query holds thrv = +inf and passes the test only with ub = +inf.
+    //   So for every later tile T' and every query q, now and at any later time: ub[q][T'] <= score(T') <= score < thr_min <= thrv[q]
+    //   (padded q: ub <= score < thr_min <= +inf, so ub is not +inf): the per-query test fails for all 32 columns, which is exactly
+    //   the rule by which the Z-curve walk skips a tile.  The stop skips nothing that the tests would not have skipped one by one.
+    //   * a 0x7f80 score ("visit": the bound pass could not bound the tile, or the tile holds the query itself) reads as +inf, and
+    //     +inf < thr_min is false for every thr_min, NaN included: such tiles sort first and the walk cannot end in front of one.
+    //   * while some real query's list is not full its thrv, and with it thr_min, is -inf: nothing is below it, the walk cannot end.
+    // The wave's own tile W is visited FIRST, whatever its place in the order (it is skipped there).  Its score is 0x7f80 like that of
+    // every tile some query nearly touches, and among equal scores the key ranks by tile number: the walk would open with the
+    // lowest-numbered of them and set its first thresholds from a tile that holds few of the neighbours.  Measured (tools/knn7_stats.py,
+    // 32 x 4096 x 64): admitted candidates per half-lane 33 -> 60, drains 7.8 -> 9.3 per wave without this.  The first call happens
+    // while every real threshold is -inf, where the test passes for any tile, so returning W untested is the same decision.
+    bool own_first = true;
+    auto find_next_sorted = [&]() -> int {
+        if (own_first) {
+            own_first = false;
+            if constexpr (!FULLT) ++stat_fn;
+            return W;
+        }
+        while (spos < nt) {
+            const uint32_t key = (uint32_t)(spos < 64 ? __builtin_amdgcn_readlane((int)ord0, spos) : __builtin_amdgcn_readlane((int)ord1, spos - 64));
+            if (knn7_score_bound(key >> 8) < thr_min) {      // (statistics: the walk was ended here iff it made fewer than nt tests)
+                spos = nt;
+                break;
+            }
+            ++spos;
+            const int T = (int)(key & 0xffu);
+            if (T == W) continue;                       // visited first
+            if constexpr (!FULLT) ++stat_fn;
+            const float ub = __uint_as_float((uint32_t)ubt[T * 32 + col] << 16);
+            if (__any(ub >= thrv)) return T;
+        }
+        return -1;
+    };
     auto find_next = [&]() -> int {
+        if constexpr (SORTED) return find_next_sorted();
         if constexpr (ONFLY && CP == 32) { if (ubq) return find_next_tab(); }
         if constexpr (!ONFLY && CP == 32 && SPLIT == 1) return find_next_lds8();
         return find_next_walk();
@@ -1746,6 +1888,12 @@ __global__ __launch_bounds__(WAVES * SPLIT * 64, ((SPLIT > 1 && CP == 2) ? 3 : K
         const float pK = __shfl_xor(tK, 32, 64), pH = __shfl_xor(tH, 32, 64);
         const float thr = fmaxf(fmaxf(tK, pK), fminf(tH, pH));
         thrv = q_ok ? thr : INFINITY;
+        if constexpr (SORTED) {         // thresholds change here and nowhere else: the stop test's operand, once per drain (padded: +inf)
+            float m = thrv;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+            thr_min = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m)));
+        }
         if constexpr (SPLIT > 1) {      // publish this wave's bounds, then take the others' into account
             thr_sh[(sw * 2 + 0) * 64 + lane] = thr;
             t3v = knn_img_inv(kh[M3 - 1]);
@@ -2190,7 +2338,19 @@ int knn7_launch(const KnnCall& a)
             return LPD_OK;
         }
     }
-    if (N % 32 == 0 && !branchy && !dbg) go(knn7_kernel<CP, KMAX, WAVES, ONFLY, true>);      // whole tiles: branch-free tile body
+    // The table in LDS and short lists: the walk in bound order (see knn7_kernel).  LPD_DEBUG=no-knn-sorted: the Z-curve walk, for A/B.
+    constexpr bool sorted_built = CP == 32 && !ONFLY && KMAX <= 20;
+    static const bool sorted_on = lpd_debug("knn-sorted", 1) != 0;
+    const bool fullt = N % 32 == 0 && !branchy && !dbg;      // whole tiles: branch-free tile body
+    if constexpr (sorted_built) {
+        if (sorted_on) {
+            if (fullt) go(knn7_kernel<CP, KMAX, WAVES, ONFLY, true, 1, true>);
+            else go(knn7_kernel<CP, KMAX, WAVES, ONFLY, false, 1, true>);
+            LPD_CHECK_LAUNCH("lpd_knn(best-first, bound order)");
+            return LPD_OK;
+        }
+    }
+    if (fullt) go(knn7_kernel<CP, KMAX, WAVES, ONFLY, true>);
     else go(knn7_kernel<CP, KMAX, WAVES, ONFLY, false>);
     LPD_CHECK_LAUNCH("lpd_knn(best-first)");
     return LPD_OK;

@@ -20,6 +20,15 @@ for name, feat in (("xyz", ops.transpose(xs.view(B, N, 3))), ("feat64", None)):
         if k >= 12:
             ph = raw.view(-1, 32, k)[:, 0, 5:12].float()
             print(name, "drain batches/wave %.1f; cycles/wave: advance %.0f  exact tile %.0f  select+queue %.0f  drain %.0f  total %.0f; bound tests %.1f" % tuple(ph.mean(0).tolist()), flush=True)
+            if name == "feat64" and k >= 16 and os.environ.get("LPD_DEBUG", "").find("no-knn-sorted") < 0:
+                # walk in bound order: the sorted keys (score image << 8 | tile) are in slots 12 .. 15 of the wave's rows; a wave that made
+                # fewer than nt tests was ended by the stop rule and never looked at the rest
+                nt = (N + 31) // 32
+                tests = ph[:, 6]
+                first = raw.view(-1, 32, k)[:, 0, 12]
+                print(name, "walk in bound order: tiles never looked at/wave %.1f of %d; waves ended by the stop %.1f %%; first tile is the wave's own %.1f %%" % (
+                    (nt - tests).mean(), nt, 100.0 * (tests < nt).float().mean(),
+                    100.0 * ((first & 0xff) == (torch.arange(first.numel(), device=first.device) % nt)).float().mean()), flush=True)
         print(name, label, "tiles visited/wave %.1f  sum of the drains' fullest lanes %.1f  drains %.1f  admitted per half-lane %.1f / %.1f" % (
             w[:, 0].mean(), w[:, 1].mean(), w[:, 3].mean(), st[:, 2].mean(), st[:, 4].mean()), flush=True)
     for impl in (4, 6):
