@@ -1062,6 +1062,63 @@ int lpd_map_localize(const float* points, int ld, int rows, const int32_t* offse
                      float inv_cell, const long long* keys, const float* surf, long long capacity, const float* dmax, int iters,
                      int min_inliers, float max_flat, double* pose, int32_t* info, long long* sums, long long* cell, void* ws, void* stream);
 
+/*
+ * LiDAR odometry (csrc/lpd_odom.hip; arithmetic in csrc/lpd_odom_math.h): scan poses for a drive from its scans alone, in the
+ * KISS-ICP style -- a sliding local voxel map and a constant-velocity start.  It is lpd_map_insert and lpd_map_localize run in turn,
+ * scan after scan; the calls below are the three things that chain lacked, each made so that the chain never waits for the host.  This
+ * comment is the specification, and lpd_odom_math.h settles every detail it leaves open.  Float64 with + - * / sqrt only, every
+ * operation rounded once, nothing contracted; integer atomics only; no barrier across workgroups; no read-back; every address that
+ * comes from data is masked or checked first; the same bits in every launch.
+ *
+ * lpd_odom_predict.  pose [S][12] float64 IN and OUT, pred [S][12] float64 OUT (not pose), 0 <= t < S, first_motion [12] float64 on
+ * the device or NULL.  One thread.  pred[t] and pose[t] are both set to the start of scan t (lpd_odom_predict_pose):
+ *   t == 0   pose[0], a bit copy
+ *   t == 1   pose[0], a bit copy; with a first_motion, pose[0] composed with it (lpd_map_compose)
+ *   t >= 2   c = lpd_map_candidate(P[t-2], P[t-1], P[t-1]) = P[t-1] (P[t-2]^-1 P[t-1]), its rotation renormalised through the quaternion
+ *            exactly as lpd_map_blend(c, c, 0.0) does it.  P[t-1] not finite: that pose, a bit copy -- the scan is then invalid for
+ *            lpd_map_localize and counts as lost.  P[t-2] not finite: P[t-1], a bit copy.
+ *
+ * lpd_odom_accept.  pred, pose as above (pose[t] now holds what lpd_map_localize left); info [S][4] int32 = lpd_map_localize's rows;
+ * offsets [S+1] int32, len = offsets[t+1] - offsets[t]; share_q = rint(min_share * 1024) made on the host, 0 .. 1024; max_jump metres,
+ * 0 .. 1e6; insert_pose [S][12] float64 OUT; state [S] int32 OUT.  One thread.  Scan t >= 1 is ACCEPTED iff info[t][0] == 1, at least
+ * one step was applied (info[t][1] >= 1), len > 0, (int64) info[t][3] * 1024 >= (int64) share_q * len, and the squared translation
+ * between pose[t] and pred[t] (the three differences, then lpd_pgo_dot3) is <= max_jump * max_jump.  Scan 0 is accepted iff its pose
+ * is finite and len > 0.  Accepted: insert_pose[t] = pose[t], state[t] = 1.  Otherwise: pose[t] = pred[t] bit for bit, insert_pose[t] =
+ * twelve NaNs, state[t] = 0 -- lpd_map_insert then drops the scan's rows by its own rule 2, so a lost scan never blurs the map.
+ *
+ * lpd_map_crop: lpd_map_rehash with a predicate -- the sliding map.  Keys are never removed from a table (the lookup relies on that),
+ * so a smaller map is a NEW table.  keys_in / acc_in / capacity_in the old table, keys / acc / capacity the new one (cleared by the
+ * caller); centre_pose [12] float64 and origin [3] float64 on the device; inv_cell as lpd_map_insert takes it; 0 <= keep_cells <= 2^21.
+ * The centre cell qc is the cell of centre_pose's translation by the insert's own rule: u = (float)(t - origin) (lpd_map_rel), qc_c =
+ * lpd_map_index(u_c, inv_cell).  A cell q = unkey(key) goes into the new table, by rule 4 of lpd_map_insert with its sums and count as
+ * they are, iff |q_c - qc_c| <= keep_cells on all three axes, in integers.  A centre that is not finite or has no cell keeps every cell.
+ * info [5] int64, ADDED to: the first four as lpd_map_rehash (rows = the kept cells' counts, -, rows lost to a full table, cells
+ * created), the fifth the cells left behind.  The mapping key -> sums of the kept cells does not depend on slot placement on either side.
+ *
+ * lpd_map_touch + lpd_map_surface_touched: the surf rows of the cells that an insert changed, and no others.  surf is indexed by slot,
+ * and a cell's row depends only on the cells within `reach` of it; so after lpd_map_insert of some scans, lpd_map_touch of the same
+ * scans and lpd_map_surface_touched, surf equals a full lpd_map_surface of the same table bit for bit, for any sequence of inserts into
+ * one table.  (A new table -- a growth, a crop -- needs the full lpd_map_surface once.)
+ *   lpd_map_touch   points .. inv_cell exactly as the lpd_map_insert that went before it; keys / capacity the table AFTER that insert,
+ *                   only read; reach 1 or 2; dirty [capacity] bytes.  The rows are walked as lpd_map_insert walks them (rule 5 there) and
+ *                   dropped as it drops them (rule 2; a chunk that is not read marks nothing).  For each row's cell q the (2 reach + 1)^3
+ *                   cells q + d are looked up (lpd_loc_find) and dirty[slot] = 1 is stored for every one found.
+ *   lpd_map_surface_touched   where dirty[slot] is set, surf's row by lpd_loc_surface (lpd_map_surface's own function) and
+ *                   dirty[slot] = 0; one thread a MARKED slot (the marked slots of 8192 are gathered per workgroup first).  dirty and surf
+ *                   16-byte aligned.  info [2] int64 as lpd_map_surface, ADDED to, for the rows written.
+ */
+#define LPD_ODOM_SHARE_UNITS 1024          /* share_q counts 1/1024ths of a scan's rows */
+#define LPD_ODOM_MAX_KEEP_CELLS 2097152    /* 2^21: beyond it a crop keeps everything anyway */
+int lpd_odom_predict(double* pose, double* pred, int S, int t, const double* first_motion, void* stream);
+int lpd_odom_accept(const double* pred, double* pose, const int32_t* info, const int32_t* offsets, int S, int t, int share_q, double max_jump,
+                    double* insert_pose, int32_t* state, void* stream);
+int lpd_map_crop(const long long* keys_in, const long long* acc_in, long long capacity_in, const double* centre_pose, const double* origin,
+                 float inv_cell, int keep_cells, long long* keys, long long* acc, long long capacity, long long* info, void* stream);
+int lpd_map_touch(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,
+                  const double* origin, float inv_cell, const long long* keys, long long capacity, int reach, unsigned char* dirty, void* stream);
+int lpd_map_surface_touched(const long long* keys, const long long* acc, long long capacity, int reach, int min_cells, float* surf,
+                            unsigned char* dirty, long long* info, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

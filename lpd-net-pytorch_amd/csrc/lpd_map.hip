@@ -21,6 +21,7 @@
 
 #include "lpd_common.h"
 #include "lpd_map_math.h"
+#include "lpd_map_table.h"
 #include "lpd_scan_chunk.h"
 
 namespace {
@@ -43,36 +44,6 @@ __global__ __launch_bounds__(MP_T) void correct_kernel(const double* __restrict_
     const int made = lpd_map_correct(poses, (const int64_t*)D, S, node_scan, node_pose, V, i, o);
     for (int k = 0; k < 12; ++k) out[(size_t)12 * i + k] = o[k];
     atomicAdd(info + (made ? 0 : 1), 1);
-}
-
-// (key, sums) into the caller's table: 0 lost, 1 added to a cell that was there, 2 added to a cell this call created.  keys never
-// change once set, so a key that is read is final, and a slot that reads empty is settled by the compare-and-swap.
-__device__ __forceinline__ int mp_global_insert(long long* __restrict__ keys, long long* __restrict__ acc, long long capacity, long long key,
-                                                long long sx, long long sy, long long sz, long long m)
-{
-    const u64 mask = (u64)capacity - 1;
-    u64 s = lpd_map_mix(key) & mask;
-    const int probes = lpd_map_probes(capacity);
-    for (int p = 0; p < probes; ++p, s = (s + 1) & mask) {
-        long long cur = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int created = 0;
-        if (cur == LPD_MAP_EMPTY) {
-            cur = (long long)atomicCAS((u64*)(keys + s), (u64)LPD_MAP_EMPTY, (u64)key);
-            if (cur == LPD_MAP_EMPTY) {
-                cur = key;
-                created = 1;
-            }
-        }
-        if (cur == key) {
-            u64* a = (u64*)(acc + 4 * s);
-            atomicAdd(a + 0, (u64)sx);
-            atomicAdd(a + 1, (u64)sy);
-            atomicAdd(a + 2, (u64)sz);
-            atomicAdd(a + 3, (u64)m);
-            return 1 + created;
-        }
-    }
-    return 0;
 }
 
 template <bool DIRECT>
@@ -146,7 +117,7 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
                 }
             }
             if (!placed) {
-                const int r = mp_global_insert(keys, acc, capacity, key, U[0], U[1], U[2], 1);
+                const int r = lpd_map_table_add(keys, acc, capacity, key, U[0], U[1], U[2], 1);
                 if (r) ++n_ins; else ++n_lost;
                 if (r == 2) ++n_new;
             }
@@ -158,8 +129,8 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
             const u64 key = lkey[s];
             if (key != (u64)LPD_MAP_EMPTY) {
                 const u64 m = lacc[4 * s + 3];
-                const int r = mp_global_insert(keys, acc, capacity, (long long)key, (long long)lacc[4 * s + 0], (long long)lacc[4 * s + 1],
-                                               (long long)lacc[4 * s + 2], (long long)m);
+                const int r = lpd_map_table_add(keys, acc, capacity, (long long)key, (long long)lacc[4 * s + 0], (long long)lacc[4 * s + 1],
+                                                (long long)lacc[4 * s + 2], (long long)m);
                 if (r) n_ins += m; else n_lost += m;
                 if (r == 2) ++n_new;
             }
@@ -182,7 +153,7 @@ __global__ __launch_bounds__(MP_T) void rehash_kernel(const long long* __restric
     const long long key = keys_in[s];
     if (key < 0) return;
     const long long m = acc_in[4 * s + 3];
-    const int r = mp_global_insert(keys, acc, capacity, key, acc_in[4 * s + 0], acc_in[4 * s + 1], acc_in[4 * s + 2], m);
+    const int r = lpd_map_table_add(keys, acc, capacity, key, acc_in[4 * s + 0], acc_in[4 * s + 1], acc_in[4 * s + 2], m);
     atomicAdd((u64*)info + (r ? 0 : 2), (u64)m);
     if (r == 2) atomicAdd((u64*)info + 3, (u64)1);
 }

@@ -1792,6 +1792,191 @@ def map_localize(points, offsets, poses, origin, inv_cell, keys, surf, dmax, min
     return pose, info, sums, cells
 
 
+# LiDAR odometry (csrc/lpd_odom.hip)
+ODOM_SHARE_UNITS, ODOM_MAX_KEEP_CELLS = _defines("ODOM", "SHARE_UNITS", "MAX_KEEP_CELLS")
+ODOM_MAX_JUMP = 1.0e6
+
+
+def _odom_whole(what, v, name, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what}: {name}={v!r} (an integer in {lo} .. {hi})")
+    return int(v)
+
+
+def _odom_poses(what, named, S=None):
+    """[S, 12] float64 tensors that a call writes in place: contiguous as they are, on one device -> S"""
+    dev = None
+    for name, t in named:
+        _req(t, name, torch.float64)
+        if t is None:
+            raise TypeError(f"{what}: {name} is a tensor")
+        if t.dim() != 2 or t.shape[1] != 12 or not t.is_contiguous() or not 1 <= t.shape[0] <= DRIVE_MAX_SCANS:
+            raise ValueError(f"{what}: {name} must be a contiguous [S, 12] tensor with 1 <= S <= 2^22, got {tuple(t.shape)}")
+        S = t.shape[0] if S is None else S
+        if t.shape[0] != S:
+            raise ValueError(f"{what}: {name} holds {t.shape[0]} poses; S = {S}")
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}, not on {dev}")
+    return S
+
+
+def odom_predict(pose, pred, t, first_motion=None):
+    """The constant-velocity start of scan t (lpd_odom_predict; definition in include/lpd_hip.h): pose, pred [S, 12] float64 on the
+    device, written IN PLACE -- pred[t] = pose[t] = pose[t-1] (pose[t-2]^-1 pose[t-1]), pose[0] for t <= 1 (composed with first_motion
+    [12] float64 on the device for t == 1 when one is given).  Nothing is read back."""
+    what = "odom_predict"
+    S = _odom_poses(what, (("pose", pose), ("pred", pred)))
+    if pose.data_ptr() == pred.data_ptr():
+        raise ValueError(f"{what}: pred must not be pose")
+    t = _odom_whole(what, t, "t", 0, S - 1)
+    if first_motion is not None:
+        _req(first_motion, "first_motion", torch.float64)
+        if tuple(first_motion.shape) != (12,) or not first_motion.is_contiguous() or first_motion.device != pose.device:
+            raise ValueError(f"{what}: first_motion must be a contiguous [12] tensor on {pose.device}, got {tuple(first_motion.shape)}")
+    _call("odom_predict", _lib.load().lpd_odom_predict, _ptr(pose), _ptr(pred), S, t, _ptr(first_motion), _stream())
+
+
+def odom_share_q(min_share, what="odom_accept"):
+    """min_share in 0 .. 1 -> share_q = rint(min_share * 1024), half to even"""
+    if isinstance(min_share, bool) or not isinstance(min_share, numbers.Real) or not 0.0 <= float(min_share) <= 1.0:
+        raise ValueError(f"{what}: min_share={min_share!r} outside 0 .. 1")
+    return int(round(float(min_share) * ODOM_SHARE_UNITS))
+
+
+def odom_accept(pred, pose, info, offsets, t, share_q, max_jump, insert_pose, state):
+    """The decision on scan t after its localisation (lpd_odom_accept): pred, pose, insert_pose [S, 12] float64, info [S, 4] int32
+    (map_localize's), offsets [S+1] int32 and state [S] int32 on the device; pose[t], insert_pose[t] and state[t] are written IN PLACE.
+    share_q = odom_share_q(min_share); max_jump metres.  Nothing is read back."""
+    what = "odom_accept"
+    S = _odom_poses(what, (("pred", pred), ("pose", pose), ("insert_pose", insert_pose)))
+    _req(info, "info", torch.int32)
+    _req(state, "state", torch.int32)
+    if info is None or state is None:
+        raise TypeError(f"{what}: info and state are tensors")
+    offsets = _drive_offsets(what, offsets, S)
+    if tuple(info.shape) != (S, 4) or not info.is_contiguous():
+        raise ValueError(f"{what}: info must be a contiguous [S, 4] = ({S}, 4) tensor, got {tuple(info.shape)}")
+    if tuple(state.shape) != (S,) or not state.is_contiguous():
+        raise ValueError(f"{what}: state must be a contiguous [S] = ({S},) tensor, got {tuple(state.shape)}")
+    if len({pred.device, info.device, offsets.device, state.device}) != 1:
+        raise ValueError(f"{what}: the poses, info, offsets and state must be on one device")
+    if len({pred.data_ptr(), pose.data_ptr(), insert_pose.data_ptr()}) != 3:
+        raise ValueError(f"{what}: pred, pose and insert_pose must be three tensors")
+    t = _odom_whole(what, t, "t", 0, S - 1)
+    share_q = _odom_whole(what, share_q, "share_q", 0, ODOM_SHARE_UNITS)
+    if isinstance(max_jump, bool) or not isinstance(max_jump, numbers.Real) or not 0.0 <= float(max_jump) <= ODOM_MAX_JUMP:
+        raise ValueError(f"{what}: max_jump={max_jump!r} outside 0 .. {ODOM_MAX_JUMP:g} m")
+    _call("odom_accept", _lib.load().lpd_odom_accept, _ptr(pred), _ptr(pose), _ptr(info), _ptr(offsets), S, t, share_q, float(max_jump),
+          _ptr(insert_pose), _ptr(state), _stream())
+
+
+def map_crop_table(capacity, device):
+    """An empty table for map_crop -> (keys, acc, info [4] = a view of the first four of info5, info5 [5] int64); keys / acc / info serve
+    map_insert afterwards"""
+    keys, acc, _ = map_table(capacity, device)
+    info5 = torch.zeros((5,), dtype=torch.int64, device=device)
+    return keys, acc, info5[:4], info5
+
+
+def map_crop(keys_in, acc_in, centre_pose, origin, inv_cell, keep_cells, keys, acc, info5):
+    """The cells of one table within keep_cells cells of centre_pose's cell into another, cleared one (lpd_map_crop): the sliding map.
+    centre_pose [12] float64 and origin [3] float64 on the device; info5 [5] int64 is added to (rows, -, rows lost, cells created, cells
+    left behind).  A centre that is not finite keeps every cell.  Nothing is read back."""
+    what = "map_crop"
+    _req(info5, "info5", torch.int64)
+    if info5 is None or tuple(info5.shape) != (5,) or not info5.is_contiguous():
+        raise ValueError(f"{what}: info5 must be a contiguous [5] int64 tensor")
+    cap = _map_table(what, keys, acc, info5[:4])
+    cap_in = _map_table(what, keys_in, acc_in, info5[:4])
+    _req(centre_pose, "centre_pose", torch.float64)
+    _req(origin, "origin", torch.float64)
+    if centre_pose is None or origin is None:
+        raise TypeError(f"{what}: centre_pose and origin are tensors")
+    if tuple(centre_pose.shape) != (12,) or not centre_pose.is_contiguous() or tuple(origin.shape) != (3,):
+        raise ValueError(f"{what}: centre_pose must be a contiguous [12] and origin a [3] tensor, got {tuple(centre_pose.shape)} and {tuple(origin.shape)}")
+    if len({keys_in.device, keys.device, centre_pose.device, origin.device}) != 1:
+        raise ValueError(f"{what}: both tables, centre_pose and origin must be on one device")
+    if keys_in.data_ptr() == keys.data_ptr() or acc_in.data_ptr() == acc.data_ptr():
+        raise ValueError(f"{what}: the new table must not be the old one")
+    inv_cell = float(inv_cell)
+    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    keep_cells = _odom_whole(what, keep_cells, "keep_cells", 0, ODOM_MAX_KEEP_CELLS)
+    _call("map_crop", _lib.load().lpd_map_crop, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(centre_pose), _ptr(origin.contiguous()), inv_cell,
+          keep_cells, _ptr(keys), _ptr(acc), cap, _ptr(info5), _stream())
+
+
+def _map_dirty(what, dirty, cap, device):
+    _req(dirty, "dirty", torch.uint8)
+    if dirty is None or tuple(dirty.shape) != (cap,) or not dirty.is_contiguous() or dirty.device != device or dirty.data_ptr() % 16:
+        raise ValueError(f"{what}: dirty must be a contiguous, 16-byte aligned [capacity] = ({cap},) uint8 tensor on {device}")
+
+
+def map_touch(points, offsets, poses, origin, inv_cell, keys, dirty, reach=1, scan0=0, scan1=None):
+    """Marks the slots whose surf rows an insert changed (lpd_map_touch): the arguments of the map_insert that went before it, keys the
+    table after that insert, dirty [capacity] uint8 written IN PLACE (1 for every cell within `reach` of an inserted row's cell).
+    Nothing is read back."""
+    what = "map_touch"
+    _req(points, "points")
+    _req(origin, "origin", torch.float64)
+    _req(keys, "keys", torch.int64)
+    poses, S = _drive_poses(what, poses)
+    if points is None or origin is None or keys is None:
+        raise TypeError(f"{what}: points, origin and keys are tensors")
+    ld = _scan_points(what, points)
+    offsets = _drive_offsets(what, offsets, S)
+    if tuple(origin.shape) != (3,):
+        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
+    cap = keys.shape[0] if keys.dim() == 1 else 0
+    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
+    _map_dirty(what, dirty, cap, keys.device)
+    if len({points.device, offsets.device, poses.device, origin.device, keys.device}) != 1:
+        raise ValueError(f"{what}: points, offsets, poses, origin and the table must be on one device")
+    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
+    if not 0 <= scan0 < scan1 <= S:
+        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
+    inv_cell = float(inv_cell)
+    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    reach, _ = map_surface_params(what, reach, LOC_MIN_CELLS)
+    _call("map_touch", _lib.load().lpd_map_touch, _ptr(points), ld, points.shape[0], _ptr(offsets), _ptr(poses), S, scan0, scan1,
+          _ptr(origin.contiguous()), inv_cell, _ptr(keys), cap, reach, _ptr(dirty), _stream())
+
+
+def map_surface_touched(keys, acc, surf, dirty, reach=1, min_cells=5, info=None):
+    """The surf rows of the marked slots, remade IN PLACE, and the marks cleared (lpd_map_surface_touched): keys / acc the table, surf
+    [capacity, 8] fp32 (map_surface's, or zeros for a table that was empty), dirty [capacity] uint8 from map_touch -> info [2] int64 as
+    map_surface's, for the rows written (a given info is added to).  After map_insert + map_touch + this, surf equals map_surface of
+    the table bit for bit.  Nothing is read back."""
+    what = "map_surface_touched"
+    reach, min_cells = map_surface_params(what, reach, min_cells)
+    _req(keys, "keys", torch.int64)
+    _req(acc, "acc", torch.int64)
+    _req(surf, "surf")
+    if keys is None or acc is None or surf is None:
+        raise TypeError(f"{what}: keys, acc and surf are tensors")
+    cap = keys.shape[0] if keys.dim() == 1 else 0
+    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
+    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous() or acc.device != keys.device:
+        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor on {keys.device}, got {tuple(acc.shape)}")
+    if tuple(surf.shape) != (cap, LOC_SURF) or not surf.is_contiguous() or surf.data_ptr() % 16 or surf.device != keys.device:
+        raise ValueError(f"{what}: surf must be a contiguous, 16-byte aligned [capacity, {LOC_SURF}] = ({cap}, {LOC_SURF}) tensor on {keys.device}, "
+                         f"got {tuple(surf.shape)}")
+    _map_dirty(what, dirty, cap, keys.device)
+    if info is None:
+        info = _zeros((2,), torch.int64, keys.device)
+    else:
+        _req(info, "info", torch.int64)
+        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != keys.device:
+            raise ValueError(f"{what}: info must be a contiguous [2] int64 tensor on {keys.device}")
+    _call("map_surface_touched", _lib.load().lpd_map_surface_touched, _ptr(keys), _ptr(acc), cap, reach, min_cells, _ptr(surf), _ptr(dirty),
+          _ptr(info), _stream())
+    return info
+
+
 # ------------------------------------------------------------------------------------------------
 # geometric verification of retrieved places (csrc/lpd_align.hip)
 # ------------------------------------------------------------------------------------------------
