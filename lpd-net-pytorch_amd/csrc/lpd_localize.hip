@@ -6,10 +6,11 @@
 //            three-row Jacobi of lpd_icp_math.h.  The only place that divides in float64 (lpd_map_mean) and the only reader of acc.
 //   init     one thread per scan: its validity, info = (1 | -1, 0, 0, 0), and into ws its fp32 world pose (lpd_map_rel), its centre g
 //            (float64) and g32.
-//   pass     THE HOT PATH.  grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, LC_T = 256 threads, the chunk staged by the loader of
-//            insert_kernel (lpd_scan_chunk.h); the fp32 poses, centres and validity of its scans come from ws into LDS (LC_CAP = 64 of
-//            them; a chunk of more scans reads ws per row -- the same bits).  A row is a gather-latency problem: 27 independent probe
-//            chains.  The FIRST probe of all 27 cells is loaded before any is compared (lpd_loc_find_after takes the chain from there),
+//   pass     THE HOT PATH.  grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, LC_T = 256 threads, the chunk found, checked and
+//            staged by the prologue and loader of insert_kernel (lpd_scan_chunk.h: of_call, span_ok, load, poses); the fp32 poses,
+//            centres and validity of its scans come from ws into LDS (LC_CAP = 64 of them; a chunk of more scans reads ws per row --
+//            the same bits).  A row is a gather-latency problem: 27 independent probe chains.  The FIRST probe of all 27 cells is
+//            loaded before any is compared (lpd_map_find_batch of lpd_map_table.h, which touch_kernel of lpd_odom.hip runs as well),
 //            then the first 16 bytes of the found slots' surf rows (the centroid) feed the running minimum, and the winner's second 16
 //            bytes (normal, flatness) decide the correspondence.  acc is never touched and nothing is divided.  The table was written by
 //            earlier launches: plain loads.
@@ -24,6 +25,7 @@
 
 #include "lpd_common.h"
 #include "lpd_loc_math.h"
+#include "lpd_map_table.h"
 #include "lpd_scan_chunk.h"
 
 namespace {
@@ -98,9 +100,6 @@ __device__ __forceinline__ long long lc_wave_sum(long long v)
     return v;
 }
 
-// the cell of neighbour e of the 27: ascending dz, dy, dx
-__device__ __forceinline__ int lc_neighbour(const int* q, int e, int64_t* key) { return lpd_loc_neighbour(q, e % 3 - 1, (e / 3) % 3 - 1, e / 9 - 1, key); }
-
 __global__ __launch_bounds__(LC_T) void loc_pass_kernel(const float* __restrict__ points, int ld, int rows, const int32_t* __restrict__ offsets,
                                                         int scan0, int scan1, float inv_cell, const long long* __restrict__ keys,
                                                         const float* __restrict__ surf, long long capacity, const LcState* __restrict__ ws,
@@ -114,19 +113,10 @@ __global__ __launch_bounds__(LC_T) void loc_pass_kernel(const float* __restrict_
     __shared__ int sval[LC_CAP];
     __shared__ u64 lsum[LC_CAP * LPD_ICP_SUMS];
     const int tid = threadIdx.x, lane = tid & 63;
-    const long long lo = offsets[scan0], hi = offsets[scan1];      // 0 <= scan0 < scan1 <= S: the host's check
-    if (!(lo >= 0 && lo <= hi && hi <= rows)) return;              // uniform: nothing is read
-    const long long c0 = (long long)blockIdx.x * LC_CH;
-    const long long g0 = c0 > lo ? c0 : lo, g1 = c0 + LC_CH < hi ? c0 + LC_CH : hi;
-    if (g0 >= g1) return;                                          // uniform
-    const int cn = (int)(g1 - g0);                                 // 1 .. 1024 rows, all in [lo, hi) within [0, rows)
-    Chunk::find_span(offsets, scan0, scan1, g0, cn, span, tid);
-    __syncthreads();
-    const int i_lo = span[0], i_hi = span[1];      // both in [scan0, scan1 - 1]
-    int bad = !(i_lo <= i_hi && (long long)offsets[i_lo] <= g0 && g1 - 1 < (long long)offsets[i_hi + 1]);      // lpd_map_chunk_ok
-    if (!bad)
-        for (int i = i_lo + tid; i <= i_hi; i += LC_T) bad |= offsets[i] > offsets[i + 1];
-    if (__syncthreads_or(bad)) {                   // not read: its rows have no correspondence
+    long long g0;
+    int cn, i_lo, i_hi;
+    if (!Chunk::of_call(offsets, rows, scan0, scan1, &g0, &cn)) return;                      // uniform
+    if (!Chunk::span_ok(offsets, scan0, scan1, g0, cn, span, tid, &i_lo, &i_hi)) {           // not read: its rows have no correspondence
         if (cell)
             for (int j = tid; j < cn; j += LC_T) cell[g0 + j] = -1;
         return;
@@ -198,22 +188,9 @@ __global__ __launch_bounds__(LC_T) void loc_pass_kernel(const float* __restrict_
             float w[3], p[3];
             int q[3];
             if (lpd_loc_world(r, inv_cell, buf[3 * j + 0], buf[3 * j + 1], buf[3 * j + 2], w, q) && lpd_loc_centred(w, g32, p)) {
-                // the first probe of all 27 chains, before any is compared
-                int64_t first[27], slot[27];
-#pragma unroll
-                for (int e = 0; e < 27; ++e) {
-                    int64_t nk = 0;
-                    const int in = lc_neighbour(q, e, &nk);
-                    slot[e] = in ? lpd_map_slot(nk, capacity) : 0;
-                    first[e] = K[slot[e]];
-                }
-                // each chain to its end: the slot of the cell, or -1
-#pragma unroll
-                for (int e = 0; e < 27; ++e) {
-                    int64_t nk = 0;
-                    const int in = lc_neighbour(q, e, &nk);
-                    slot[e] = in ? lpd_loc_find_after(K, capacity, nk, slot[e], first[e]) : -1;
-                }
+                // the slots of the 27 cells, or -1: the first probe of all 27 chains before any is compared
+                int64_t slot[27];
+                lpd_map_find_batch<1, 3>(K, capacity, q, -1, [&](int e, int64_t at) { slot[e] = at; });
                 // the centroids of the present cells, the running minimum in ascending key order
                 float best = INFINITY;
                 int64_t at = -1;
@@ -302,8 +279,6 @@ __global__ __launch_bounds__(LC_T) void loc_step_kernel(int scan0, int scan1, in
     }
 }
 
-bool lc_capacity_ok(long long c) { return c >= LPD_MAP_MIN_CAPACITY && c <= LPD_MAP_MAX_CAPACITY && (c & (c - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int lpd_map_surface(const long long* keys, const long long* acc, long long capacity, int reach, int min_cells, float* surf,
@@ -311,10 +286,8 @@ extern "C" int lpd_map_surface(const long long* keys, const long long* acc, long
 {
     hipStream_t stream = (hipStream_t)stream_;
     LPD_CHECK_ARG(keys && acc && surf && info, "lpd_map_surface: null pointer");
-    LPD_CHECK_ARG(lc_capacity_ok(capacity), "lpd_map_surface: capacity=%lld is not a power of two in 16 .. 2^36", capacity);
-    LPD_CHECK_ARG(reach == 1 || reach == 2, "lpd_map_surface: reach=%d (1 or 2)", reach);
-    const int cells = (2 * reach + 1) * (2 * reach + 1) * (2 * reach + 1);
-    LPD_CHECK_ARG(min_cells >= 4 && min_cells <= cells, "lpd_map_surface: min_cells=%d outside 4 .. %d", min_cells, cells);
+    LPD_MAP_CHECK_CAPACITY("lpd_map_surface", capacity);
+    LPD_MAP_CHECK_REACH("lpd_map_surface", reach, min_cells);
     LPD_CHECK_ARG(((uintptr_t)surf & 15) == 0, "lpd_map_surface: surf must be 16-byte aligned");
     hipLaunchKernelGGL(surface_kernel, dim3((unsigned)((capacity + LC_T - 1) / LC_T)), dim3(LC_T), 0, stream, keys, acc, capacity, reach, min_cells,
                        surf, info);
@@ -334,12 +307,7 @@ extern "C" int lpd_map_localize(const float* points, int ld, int rows, const int
 {
     hipStream_t stream = (hipStream_t)stream_;
     LPD_CHECK_ARG(points && offsets && origin && keys && surf && dmax && pose && info && sums, "lpd_map_localize: null pointer");
-    LPD_CHECK_ARG(ld >= 3 && rows >= 1, "lpd_map_localize: bad dims ld=%d rows=%d (ld >= 3, rows >= 1)", ld, rows);
-    LPD_CHECK_ARG(S >= 1 && S <= LPD_DRIVE_MAX_SCANS, "lpd_map_localize: S=%d outside 1 .. 2^22", S);
-    LPD_CHECK_ARG(scan0 >= 0 && scan0 < scan1 && scan1 <= S, "lpd_map_localize: scans %d .. %d outside 0 .. S=%d", scan0, scan1, S);
-    LPD_CHECK_ARG(inv_cell >= LPD_MAP_INV_CELL_MIN && inv_cell <= LPD_MAP_INV_CELL_MAX, "lpd_map_localize: inv_cell=%g outside 1/16 .. 1024",
-                  (double)inv_cell);
-    LPD_CHECK_ARG(lc_capacity_ok(capacity), "lpd_map_localize: capacity=%lld is not a power of two in 16 .. 2^36", capacity);
+    LPD_MAP_CHECK_SCANS("lpd_map_localize", ld, rows, S, scan0, scan1, inv_cell, capacity);
     LPD_CHECK_ARG(iters >= 0 && iters <= LPD_LOC_MAX_ITERS, "lpd_map_localize: iters=%d outside 0 .. %d", iters, LPD_LOC_MAX_ITERS);
     LPD_CHECK_ARG(min_inliers >= LPD_ICP_MIN_INLIERS, "lpd_map_localize: min_inliers=%d below %d", min_inliers, LPD_ICP_MIN_INLIERS);
     LPD_CHECK_ARG(max_flat > 0.0f && max_flat <= 1.0f, "lpd_map_localize: max_flat=%g outside (0, 1]", (double)max_flat);

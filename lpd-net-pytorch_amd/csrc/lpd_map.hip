@@ -1,5 +1,5 @@
-// lpd_map.hip -- the drive map: the nodes' correction of a pose graph carried to every scan, and posed scans averaged into one global
-// voxel grid kept as a hash table.  Definition: include/lpd_hip.h; arithmetic: lpd_map_math.h.
+// lpd_map.hip -- the drive map: the nodes' correction of a pose graph carried to every scan, posed scans averaged into one global
+// voxel grid kept as a hash table, and the copy of such a table into another.  Definition: include/lpd_hip.h; arithmetic: lpd_map_math.h.
 //
 //   correct  one thread per scan: a binary search over node_scan, two rigid candidates in float64, their blend.  The only atomics are
 //            the two counters (the compiler folds a wave's adds into one).
@@ -13,7 +13,11 @@
 //              A row that finds no LDS slot in LPD_MAP_LDS_PROBES probes goes straight to the caller's table.
 //              direct form (LPD_DEBUG=map-direct): every row straight to the caller's table.
 //            Both forms add the same integers to the same keys, so the extracted map is the same.
-//   rehash   one thread per slot of an old table: its (key, sums) inserted into a new one.
+//   rehash   one thread per slot of an old table: its (key, sums) inserted into a new one (keys are never removed from a table, so a
+//   crop     smaller map is a NEW table).  ONE kernel, copy_kernel: the crop (lpd_odom_math.h) is the rehash with a predicate -- only
+//            the cells within keep_cells of the centre's cell go over.
+// Shared with lpd_odom.hip and lpd_localize.hip: the chunk's prologue and loader (lpd_scan_chunk.h: of_call, span_ok, load, poses), the
+// table insert and the entry points' argument checks (lpd_map_table.h), lpd_map_capacity_ok (lpd_map_math.h).
 // Integer atomics only: a sum does not depend on the order of its terms.  WHICH slot a key lands in depends on timing; the mapping
 // key -> (Sx, Sy, Sz, m) does not.  No barrier across workgroups.  The only address that comes from data is a slot index, masked by
 // capacity - 1; every index into offsets, poses and points is checked against its table first.
@@ -22,6 +26,7 @@
 #include "lpd_common.h"
 #include "lpd_map_math.h"
 #include "lpd_map_table.h"
+#include "lpd_odom_math.h"
 #include "lpd_scan_chunk.h"
 
 namespace {
@@ -60,26 +65,16 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
     __shared__ u64 lkey[DIRECT ? 1 : MP_LS];
     __shared__ u64 lacc[DIRECT ? 4 : 4 * MP_LS];
     const int tid = threadIdx.x;
-    const long long lo = offsets[scan0], hi = offsets[scan1];      // 0 <= scan0 < scan1 <= S: the host's check
-    if (!(lo >= 0 && lo <= hi && hi <= rows)) return;              // uniform: nothing is read
-    const long long c0 = (long long)blockIdx.x * MP_CH;
-    const long long g0 = c0 > lo ? c0 : lo, g1 = c0 + MP_CH < hi ? c0 + MP_CH : hi;
-    if (g0 >= g1) return;                                          // uniform
-    const int cn = (int)(g1 - g0);                                 // 1 .. 1024 rows, all in [lo, hi) within [0, rows)
-    if (tid < 4) cnt[tid] = 0;
+    long long g0;
+    int cn, i_lo, i_hi;
+    if (!Chunk::of_call(offsets, rows, scan0, scan1, &g0, &cn)) return;      // uniform
+    if (tid < 4) cnt[tid] = 0;                                               // the barrier of span_ok publishes these and the LDS table
     if (!DIRECT)
         for (int s = tid; s < MP_LS; s += MP_T) {
             lkey[s] = (u64)LPD_MAP_EMPTY;
             lacc[4 * s + 0] = 0; lacc[4 * s + 1] = 0; lacc[4 * s + 2] = 0; lacc[4 * s + 3] = 0;
         }
-    Chunk::find_span(offsets, scan0, scan1, g0, cn, span, tid);
-    __syncthreads();
-    const int i_lo = span[0], i_hi = span[1];      // both in [scan0, scan1 - 1]
-    // is this part of the table one?  (lpd_map_chunk_ok, its loop shared among the threads)
-    int bad = !(i_lo <= i_hi && (long long)offsets[i_lo] <= g0 && g1 - 1 < (long long)offsets[i_hi + 1]);
-    if (!bad)
-        for (int i = i_lo + tid; i <= i_hi; i += MP_T) bad |= offsets[i] > offsets[i + 1];
-    if (__syncthreads_or(bad)) {                   // not read: its rows are counted as dropped
+    if (!Chunk::span_ok(offsets, scan0, scan1, g0, cn, span, tid, &i_lo, &i_hi)) {      // not read: its rows are counted as dropped
         if (tid == 0) atomicAdd((u64*)info + 1, (u64)cn);
         return;
     }
@@ -144,21 +139,44 @@ __global__ __launch_bounds__(MP_T) void insert_kernel(const float* __restrict__ 
     if (tid < 4 && cnt[tid]) atomicAdd((u64*)info + tid, cnt[tid]);
 }
 
-__global__ __launch_bounds__(MP_T) void rehash_kernel(const long long* __restrict__ keys_in, const long long* __restrict__ acc_in, long long cap_in,
-                                                      long long* __restrict__ keys, long long* __restrict__ acc, long long capacity,
-                                                      long long* __restrict__ info)
+// Every occupied slot of one table into another, one thread per slot of the old one.  KEEP: only the cells within keep_cells of the
+// centre's cell (lpd_odom_keep); without it centre and origin are not read and info [4] is never touched.  One global add a counter
+// and workgroup, none for a counter that stayed 0: a cell's count m differs from lane to lane, so the compiler cannot fold a wave's adds.
+template <bool KEEP>
+__global__ __launch_bounds__(MP_T) void copy_kernel(const long long* __restrict__ keys_in, const long long* __restrict__ acc_in, long long cap_in,
+                                                    const double* __restrict__ centre, const double* __restrict__ origin, float inv_cell,
+                                                    int keep_cells, long long* __restrict__ keys, long long* __restrict__ acc,
+                                                    long long capacity, long long* __restrict__ info)
 {
+    __shared__ u64 cnt[4];      // rows of the copied cells, rows lost, cells created, cells left behind
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    __syncthreads();
     const long long s = (long long)blockIdx.x * MP_T + threadIdx.x;
-    if (s >= cap_in) return;
-    const long long key = keys_in[s];
-    if (key < 0) return;
-    const long long m = acc_in[4 * s + 3];
-    const int r = lpd_map_table_add(keys, acc, capacity, key, acc_in[4 * s + 0], acc_in[4 * s + 1], acc_in[4 * s + 2], m);
-    atomicAdd((u64*)info + (r ? 0 : 2), (u64)m);
-    if (r == 2) atomicAdd((u64*)info + 3, (u64)1);
+    const long long key = s < cap_in ? keys_in[s] : LPD_MAP_EMPTY;
+    if (key >= 0) {
+        bool keep = true;
+        if (KEEP) {
+            double c12[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) c12[k] = centre[k];
+            const double org[3] = {origin[0], origin[1], origin[2]};
+            int qc[3] = {0, 0, 0};
+            const int has = lpd_odom_centre_cell(c12, org, inv_cell, qc);
+            keep = lpd_odom_keep(key, has, qc, keep_cells);
+        }
+        if (!keep) {
+            atomicAdd(&cnt[3], (u64)1);
+        } else {
+            const long long m = acc_in[4 * s + 3];
+            const int r = lpd_map_table_add(keys, acc, capacity, key, acc_in[4 * s + 0], acc_in[4 * s + 1], acc_in[4 * s + 2], m);
+            atomicAdd(&cnt[r ? 0 : 1], (u64)m);
+            if (r == 2) atomicAdd(&cnt[2], (u64)1);
+        }
+    }
+    __syncthreads();
+    const int to[4] = {0, 2, 3, 4};
+    if (threadIdx.x < 4 && cnt[threadIdx.x]) atomicAdd((u64*)info + to[threadIdx.x], cnt[threadIdx.x]);
 }
-
-bool mp_capacity_ok(long long c) { return c >= LPD_MAP_MIN_CAPACITY && c <= LPD_MAP_MAX_CAPACITY && (c & (c - 1)) == 0; }
 
 }  // namespace
 
@@ -181,12 +199,7 @@ extern "C" int lpd_map_insert(const float* points, int ld, int rows, const int32
 {
     hipStream_t stream = (hipStream_t)stream_;
     LPD_CHECK_ARG(points && offsets && poses && origin && keys && acc && info, "lpd_map_insert: null pointer");
-    LPD_CHECK_ARG(ld >= 3 && rows >= 1, "lpd_map_insert: bad dims ld=%d rows=%d (ld >= 3, rows >= 1)", ld, rows);
-    LPD_CHECK_ARG(S >= 1 && S <= LPD_DRIVE_MAX_SCANS, "lpd_map_insert: S=%d outside 1 .. 2^22", S);
-    LPD_CHECK_ARG(scan0 >= 0 && scan0 < scan1 && scan1 <= S, "lpd_map_insert: scans %d .. %d outside 0 .. S=%d", scan0, scan1, S);
-    LPD_CHECK_ARG(inv_cell >= LPD_MAP_INV_CELL_MIN && inv_cell <= LPD_MAP_INV_CELL_MAX,
-                  "lpd_map_insert: inv_cell=%g outside 1/16 .. 1024 (a cell of 2^-10 .. 16 m keeps every sum inside an int64)", (double)inv_cell);
-    LPD_CHECK_ARG(mp_capacity_ok(capacity), "lpd_map_insert: capacity=%lld is not a power of two in 16 .. 2^36", capacity);
+    LPD_MAP_CHECK_SCANS("lpd_map_insert", ld, rows, S, scan0, scan1, inv_cell, capacity);
     const dim3 grid((unsigned)(((long long)rows + MP_CH - 1) / MP_CH));
     if (lpd_debug("map-direct", 0))
         hipLaunchKernelGGL(insert_kernel<true>, grid, dim3(MP_T), 0, stream, points, ld, rows, offsets, poses, scan0, scan1, origin, inv_cell, keys,
@@ -203,11 +216,24 @@ extern "C" int lpd_map_rehash(const long long* keys_in, const long long* acc_in,
 {
     hipStream_t stream = (hipStream_t)stream_;
     LPD_CHECK_ARG(keys_in && acc_in && keys && acc && info, "lpd_map_rehash: null pointer");
-    LPD_CHECK_ARG(mp_capacity_ok(capacity_in) && mp_capacity_ok(capacity), "lpd_map_rehash: capacities %lld -> %lld are not powers of two in 16 .. 2^36",
-                  capacity_in, capacity);
-    LPD_CHECK_ARG((const void*)keys_in != (const void*)keys && (const void*)acc_in != (const void*)acc, "lpd_map_rehash: the new table must not be the old one");
-    hipLaunchKernelGGL(rehash_kernel, dim3((unsigned)((capacity_in + MP_T - 1) / MP_T)), dim3(MP_T), 0, stream, keys_in, acc_in, capacity_in, keys, acc,
-                       capacity, info);
+    LPD_MAP_CHECK_TWO_TABLES("lpd_map_rehash", keys_in, acc_in, capacity_in, keys, acc, capacity);
+    hipLaunchKernelGGL(copy_kernel<false>, dim3((unsigned)((capacity_in + MP_T - 1) / MP_T)), dim3(MP_T), 0, stream, keys_in, acc_in, capacity_in,
+                       (const double*)nullptr, (const double*)nullptr, 0.0f, 0, keys, acc, capacity, info);
     LPD_CHECK_LAUNCH("lpd_map_rehash");
+    return LPD_OK;
+}
+
+extern "C" int lpd_map_crop(const long long* keys_in, const long long* acc_in, long long capacity_in, const double* centre_pose,
+                            const double* origin, float inv_cell, int keep_cells, long long* keys, long long* acc, long long capacity,
+                            long long* info, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    LPD_CHECK_ARG(keys_in && acc_in && centre_pose && origin && keys && acc && info, "lpd_map_crop: null pointer");
+    LPD_MAP_CHECK_TWO_TABLES("lpd_map_crop", keys_in, acc_in, capacity_in, keys, acc, capacity);
+    LPD_MAP_CHECK_INV_CELL("lpd_map_crop", inv_cell);
+    LPD_CHECK_ARG(keep_cells >= 0 && keep_cells <= LPD_ODOM_MAX_KEEP_CELLS, "lpd_map_crop: keep_cells=%d outside 0 .. 2^21", keep_cells);
+    hipLaunchKernelGGL(copy_kernel<true>, dim3((unsigned)((capacity_in + MP_T - 1) / MP_T)), dim3(MP_T), 0, stream, keys_in, acc_in, capacity_in,
+                       centre_pose, origin, inv_cell, keep_cells, keys, acc, capacity, info);
+    LPD_CHECK_LAUNCH("lpd_map_crop");
     return LPD_OK;
 }

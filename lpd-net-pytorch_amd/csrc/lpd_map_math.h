@@ -75,6 +75,9 @@ LPD_MAP_FN uint64_t lpd_map_mix(int64_t key)
 
 LPD_MAP_FN int64_t lpd_map_slot(int64_t key, int64_t capacity) { return (int64_t)(lpd_map_mix(key) & (uint64_t)(capacity - 1)); }
 
+// a table's capacity: a power of two in LPD_MAP_MIN_CAPACITY .. LPD_MAP_MAX_CAPACITY (every entry point's check)
+LPD_MAP_FN int lpd_map_capacity_ok(int64_t c) { return c >= LPD_MAP_MIN_CAPACITY && c <= LPD_MAP_MAX_CAPACITY && (c & (c - 1)) == 0; }
+
 // probes of one insert into a table of `capacity` slots
 LPD_MAP_FN int lpd_map_probes(int64_t capacity) { return capacity < LPD_MAP_MAX_PROBES ? (int)capacity : LPD_MAP_MAX_PROBES; }
 

@@ -1,9 +1,15 @@
 // lpd_scan_chunk.h -- one workgroup stages a chunk of the ragged scan table (points [rows][ld], offsets [S+1], one pose a scan): the
-// steps that rows_kernel (lpd_drive.hip) and insert_kernel (lpd_map.hip) share.  HIP only.  A chunk is cn <= CH consecutive rows of
-// the table from row g0 on, which belong to the consecutive scans i_lo .. i_hi.  LpdScanChunk<T, CH, CAP> serves a workgroup of T
-// threads that keeps CAP poses; the LDS arrays (buf [3 CH], rel [CAP], soff [CAP + 1], span [2]) are the kernel's and come in as
-// pointers.  Nothing here knows which kernel calls it, what a pose is relative to, or what becomes of a row.
+// steps that rows_kernel (lpd_drive.hip), insert_kernel (lpd_map.hip), touch_kernel (lpd_odom.hip) and loc_pass_kernel
+// (lpd_localize.hip) share.  HIP only.  A chunk is cn <= CH consecutive rows of the table from row g0 on, which belong to the
+// consecutive scans i_lo .. i_hi.  LpdScanChunk<T, CH, CAP> serves a workgroup of T threads that keeps CAP poses; the LDS arrays (buf
+// [3 CH], rel [CAP], soff [CAP + 1], span [2]) are the kernel's and come in as pointers.  Nothing here knows which kernel calls it, what
+// a pose is relative to, or what becomes of a row.
 //
+//   of_call    the chunk of workgroup blockIdx.x among the rows of the scans scan0 .. scan1-1 of a call (the rule of lpd_map_math.h) ->
+//              g0 and cn, or false = nothing to do; both ways out are uniform.  rows_kernel cuts its windows from a plan instead.
+//   span_ok    CONTAINS TWO BARRIERS: find_span, a barrier, lpd_map_chunk_ok with its loop shared among the threads, and the vote
+//              (__syncthreads_or) -> i_lo, i_hi and whether the chunk is read.  What a kernel wrote to LDS before the call is visible
+//              to all threads behind it; what becomes of a refused chunk is the kernel's.
 //   load       the rows' coordinates into buf, row j at floats 3 j .. 3 j + 2 (stride 3: no bank conflict).  ld == 3: the chunk is
 //              3 cn consecutive floats, copied as a FLAT array with 16-byte accesses on the aligned body (copy_in; copy_out is the way
 //              back).  ld == 4 with a 16-byte aligned table: one 16-byte load a row.  Every other table by the float.
@@ -12,9 +18,9 @@
 //              the first threads; -> whether that table was made.
 //   row_pose   the pose of row g: rel[its scan, found in soff] with the table, else pose(its scan, found in offsets) on the spot --
 //              the same callable, so the same bits by the slow road (a chunk of more than CAP scans: scans of a handful of rows).
-// None of these meets a barrier: the kernel places one behind find_span and one behind poses (uniformly, or inside the uniform
-// `if (table)`), where its own steps between them want it.  Every index that becomes an address is the caller's to have checked:
-// g0 + cn <= rows, and lo < hi <= S for the scans searched.
+// Only span_ok meets a barrier: behind poses (and behind find_span, for a kernel that calls it itself) the kernel places one (uniformly,
+// or inside the uniform `if (table)`), where its own steps between them want it.  Every index that becomes an address is the caller's
+// to have checked: g0 + cn <= rows, and lo < hi <= S for the scans searched -- what of_call and span_ok do for the host's scan0 < scan1.
 #pragma once
 #include "lpd_common.h"
 #include "lpd_drive_math.h"
@@ -85,6 +91,34 @@ struct LpdScanChunk {
     {
         if (tid == 0) span[0] = lpd_drive_scan_of(offsets, lo, hi, g0);
         if (tid == 64) span[1] = lpd_drive_scan_of(offsets, lo, hi, g0 + cn - 1);
+    }
+
+    // -> false: the call reads nothing, or this workgroup has no row.  Else cn = 1 .. CH rows from g0 on, all in [lo, hi) within [0, rows)
+    static __device__ __forceinline__ bool of_call(const int32_t* __restrict__ offsets, int rows, int scan0, int scan1, long long* g0, int* cn)
+    {
+        const long long lo = offsets[scan0], hi = offsets[scan1];
+        if (!(lo >= 0 && lo <= hi && hi <= rows)) return false;
+        const long long c0 = (long long)blockIdx.x * CH;
+        const long long a = c0 > lo ? c0 : lo, b = c0 + CH < hi ? c0 + CH : hi;
+        if (a >= b) return false;
+        *g0 = a;
+        *cn = (int)(b - a);
+        return true;
+    }
+
+    // BARRIERS INSIDE.  i_lo, i_hi: both in [scan0, scan1 - 1]; -> whether this part of the table is one, the same in every thread
+    static __device__ __forceinline__ bool span_ok(const int32_t* __restrict__ offsets, int scan0, int scan1, long long g0, int cn, int* span,
+                                                   int tid, int* i_lo, int* i_hi)
+    {
+        find_span(offsets, scan0, scan1, g0, cn, span, tid);
+        __syncthreads();
+        const int lo = span[0], hi = span[1];
+        int bad = !(lo <= hi && (long long)offsets[lo] <= g0 && g0 + cn - 1 < (long long)offsets[hi + 1]);
+        if (!bad)
+            for (int i = lo + tid; i <= hi; i += T) bad |= offsets[i] > offsets[i + 1];
+        *i_lo = lo;
+        *i_hi = hi;
+        return !__syncthreads_or(bad);
     }
 
     // pose(i) -> LpdDriveRel of scan i.  Reads offsets[i_lo .. i_lo + ns]: i_lo + ns = i_hi + 1 <= S

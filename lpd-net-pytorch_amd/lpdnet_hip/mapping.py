@@ -43,6 +43,59 @@ ROWS_PER_CELL_GUESS = 4
 MAX_DOUBLINGS = 8      # of one insert
 
 
+def first_capacity(rows):
+    """the slots of a table that is sized from the `rows` it is about to take (see above)"""
+    cap = MIN_FIRST_CAPACITY
+    while cap < 2 * (rows // ROWS_PER_CELL_GUESS) and cap < ops.MAP_MAX_CAPACITY:
+        cap *= 2
+    return cap
+
+
+def _scan_range(what, scans, S):
+    """scans: None, a (start, stop) pair or a contiguous range -> (a, b) with 0 <= a <= b <= S"""
+    if scans is None:
+        return 0, S
+    a, b = (scans.start, scans.stop) if isinstance(scans, range) else (int(v) for v in scans)
+    if isinstance(scans, range) and scans.step != 1:
+        raise ValueError(f"{what}: scans must be a contiguous range")
+    if not 0 <= a <= b <= S:
+        raise ValueError(f"{what}: scans {a} .. {b} outside 0 .. {S}")
+    return a, b
+
+
+def scan_input(what, points, lengths, device, S=None, owner="the map"):
+    """points / lengths as drive.accumulate takes them -> (rows on `device`, host lengths); S: the scans they must hold (None: 1 .. 2^22)"""
+    pts, lengths = drive._drive_input(points, lengths)
+    if S is None:
+        S = len(lengths)
+        if not 1 <= S <= ops.DRIVE_MAX_SCANS:
+            raise ValueError(f"{what}: {S} scans; 1 .. 2^22")
+    with torch.no_grad():
+        lengths = drive._lengths(lengths, S, what)
+        rows = submap._device_rows(pts, device)
+    if rows.device != device:
+        raise ValueError(f"{what}: points on {rows.device}, {owner} on {device}")
+    return rows, lengths
+
+
+def _posed_input(what, points, lengths, poses, scans, device):
+    """what VoxelMap.insert and localize_scans take -> (rows, lengths, poses [S, 12] float64 on `device`, the scans a .. b-1)"""
+    with torch.no_grad():
+        p = drive._poses(poses, device, what)
+    rows, lengths = scan_input(what, points, lengths, device, p.shape[0])
+    if p.device != device:
+        raise ValueError(f"{what}: points on {rows.device}, poses on {p.device}, the map on {device}")
+    return (rows, lengths, p) + _scan_range(what, scans, p.shape[0])
+
+
+def fit_quality(matched, lengths, m, ss):
+    """a last pass's inliers = matched / the scan's length (0 for an empty scan) and rms = sqrt(ss / m) / 1024 m (0 where m = 0)"""
+    m, n_rows = m.to(torch.float64), torch.from_numpy(np.asarray(lengths, dtype=np.float64)).to(m.device)
+    inliers = torch.where(n_rows > 0, matched.to(torch.float64) / n_rows.clamp(min=1.0), torch.zeros_like(n_rows))
+    rms = torch.where(m > 0, torch.sqrt(ss.to(torch.float64) / m.clamp(min=1.0)) / 1024.0, torch.zeros_like(m))
+    return inliers, rms
+
+
 def _plan_of(what, sub):
     plan = sub.plan if isinstance(sub, drive.DriveSubmaps) else sub
     if not isinstance(plan, drive.DrivePlan):
@@ -131,7 +184,7 @@ class VoxelMap:
             if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)):
                 raise TypeError(f"{what}: capacity must be an integer, got {type(capacity).__name__}")
             capacity = int(capacity)
-            if not ops.MAP_MIN_CAPACITY <= capacity <= ops.MAP_MAX_CAPACITY or capacity & (capacity - 1):
+            if not ops.map_capacity_ok(capacity):
                 raise ValueError(f"{what}: capacity={capacity} is not a power of two in 16 .. 2^36")
         self._first_capacity = capacity
         self.keys = self.acc = self.info = None
@@ -170,22 +223,8 @@ class VoxelMap:
         the capacity from a copy made before the call, and THE CALL IS RUN AGAIN -- at most 8 doublings a call; a table more than half
         full after a call is doubled for the next one.  Waits for the device once a run (the counters).  -> self"""
         what = "VoxelMap.insert"
-        pts, lengths = drive._drive_input(points, lengths)
+        rows, lengths, p, a, b = _posed_input(what, points, lengths, poses, scans, self.device)
         with torch.no_grad():
-            p = drive._poses(poses, self.device, what)
-            lengths = drive._lengths(lengths, p.shape[0], what)
-            S = p.shape[0]
-            if scans is None:
-                a, b = 0, S
-            else:
-                a, b = (scans.start, scans.stop) if isinstance(scans, range) else (int(v) for v in scans)
-                if isinstance(scans, range) and scans.step != 1:
-                    raise ValueError(f"{what}: scans must be a contiguous range")
-                if not 0 <= a <= b <= S:
-                    raise ValueError(f"{what}: scans {a} .. {b} outside 0 .. {S}")
-            rows = submap._device_rows(pts, self.device)
-            if rows.device != self.device or p.device != self.device:
-                raise ValueError(f"{what}: points on {rows.device}, poses on {p.device}, the map on {self.device}")
             n = int(lengths[a:b].sum())
             with torch.cuda.device(self.device):
                 if self.origin is None:
@@ -196,11 +235,7 @@ class VoxelMap:
                 self._surface = None
                 offsets = drive._scan_offsets(lengths, self.device)
                 if self.keys is None:
-                    cap = self._first_capacity
-                    if cap is None:
-                        cap = MIN_FIRST_CAPACITY
-                        while cap < 2 * (n // ROWS_PER_CELL_GUESS) and cap < ops.MAP_MAX_CAPACITY:
-                            cap *= 2
+                    cap = first_capacity(n) if self._first_capacity is None else self._first_capacity
                     self.keys, self.acc, self.info = ops.map_table(cap, self.device)
                     before = None
                 else:
@@ -336,17 +371,6 @@ class Localization:
         return int(self.poses.shape[0])
 
 
-def _scan_range(what, scans, S):
-    if scans is None:
-        return 0, S
-    a, b = (scans.start, scans.stop) if isinstance(scans, range) else (int(v) for v in scans)
-    if isinstance(scans, range) and scans.step != 1:
-        raise ValueError(f"{what}: scans must be a contiguous range")
-    if not 0 <= a <= b <= S:
-        raise ValueError(f"{what}: scans {a} .. {b} outside 0 .. {S}")
-    return a, b
-
-
 def localize_scans(vmap, points, lengths, poses, search=LocalizeSearch(), scans=None, want_cells=False):
     """Posed scans localised against a VoxelMap: trimmed point-to-plane ICP of every scan, as a whole, against the centroids and normals
     of the map's cells (lpd_map_localize) -> Localization.  points / lengths / poses / scans as VoxelMap.insert takes them, each scan in
@@ -361,16 +385,9 @@ def localize_scans(vmap, points, lengths, poses, search=LocalizeSearch(), scans=
         raise TypeError(f"{what}: search must be a LocalizeSearch, got {type(search).__name__}")
     if vmap.keys is None:
         raise ValueError(f"{what}: nothing was inserted into the map")
-    pts, lengths = drive._drive_input(points, lengths)
+    rows, lengths, p, a, b = _posed_input(what, points, lengths, poses, scans, vmap.device)
     with torch.no_grad():
-        p = drive._poses(poses, vmap.device, what)
-        lengths = drive._lengths(lengths, p.shape[0], what)
-        S = p.shape[0]
-        a, b = _scan_range(what, scans, S)
-        rows = submap._device_rows(pts, vmap.device)
-        if rows.device != vmap.device or p.device != vmap.device:
-            raise ValueError(f"{what}: points on {rows.device}, poses on {p.device}, the map on {vmap.device}")
-        dev = vmap.device
+        S, dev = p.shape[0], vmap.device
         with torch.cuda.device(dev):
             n = int(lengths[a:b].sum())
             if n == 0 or rows.shape[0] == 0:      # nothing to read: every scan keeps its pose
@@ -383,10 +400,7 @@ def localize_scans(vmap, points, lengths, poses, search=LocalizeSearch(), scans=
             surf = vmap.surface(search.reach, search.min_cells)
             pose, info, sums, cells = ops.map_localize(rows, offsets, p, vmap.origin, vmap.inv_cell, vmap.keys, surf, search.schedule(vmap.cell),
                                                        search.min_inliers, search.max_flat, a, b, want_cells)
-            m = sums[-1, :, 0].to(torch.float64)
-            n_rows = torch.from_numpy(np.asarray(lengths, dtype=np.float64)).to(dev)
-            inliers = torch.where(n_rows > 0, info[:, 3].to(torch.float64) / n_rows.clamp(min=1.0), torch.zeros_like(n_rows))
-            rms = torch.where(m > 0, torch.sqrt(sums[-1, :, 28].to(torch.float64) / m.clamp(min=1.0)) / 1024.0, torch.zeros_like(m))
+            inliers, rms = fit_quality(info[:, 3], lengths, sums[-1, :, 0], sums[-1, :, 28])
     return Localization(pose, info[:, 0] == 1, info[:, 1].contiguous(), info[:, 2].contiguous(), inliers, rms, sums, cells)
 
 

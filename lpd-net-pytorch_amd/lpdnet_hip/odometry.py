@@ -18,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from . import drive, mapping, ops, submap
+from . import drive, mapping, ops
 from ._lib import LpdHipError
 from .verify import _Frozen
 
@@ -159,10 +159,7 @@ def _run(rows, offsets, lengths, start, search, cap, dev):
             ops.map_surface_touched(keys, acc, surf, dirty, loc.reach, loc.min_cells)
         else:
             surf = ops.map_surface(keys, acc, loc.reach, loc.min_cells)[0]
-    m = last[:, 0].to(torch.float64)
-    n_rows = torch.from_numpy(np.asarray(lengths, dtype=np.float64)).to(dev)
-    inliers = torch.where(n_rows > 0, info[:, 3].to(torch.float64) / n_rows.clamp(min=1.0), torch.zeros_like(n_rows))
-    rms = torch.where(m > 0, torch.sqrt(last[:, 1].to(torch.float64) / m.clamp(min=1.0)) / 1024.0, torch.zeros_like(m))
+    inliers, rms = mapping.fit_quality(info[:, 3], lengths, last[:, 0], last[:, 1])
     fields = dict(poses=pose, valid=state == 1, steps=info[:, 1].contiguous(), refused=info[:, 2].contiguous(), inliers=inliers, rms=rms,
                   capacity=cap, keys=keys, acc=acc, origin=origin, cell=search.cell)
     return fields, torch.stack(counters), state
@@ -181,15 +178,9 @@ def estimate_poses(points, lengths, start=None, search=OdometrySearch(), device=
     if not isinstance(search, OdometrySearch):
         raise TypeError(f"{what}: search must be an OdometrySearch, got {type(search).__name__}")
     dev = drive._device(device, what)
-    pts, lengths = drive._drive_input(points, lengths)
+    rows, lengths = mapping.scan_input(what, points, lengths, dev, owner="the odometry")
     with torch.no_grad():
         S = len(lengths)
-        if not 1 <= S <= ops.DRIVE_MAX_SCANS:
-            raise ValueError(f"{what}: {S} scans; 1 .. 2^22")
-        lengths = drive._lengths(lengths, S, what)
-        rows = submap._device_rows(pts, dev)
-        if rows.device != dev:
-            raise ValueError(f"{what}: points on {rows.device}, the odometry on {dev}")
         if rows.shape[0] == 0:
             raise ValueError(f"{what}: the drive has no rows")
         with torch.cuda.device(dev):
@@ -199,9 +190,7 @@ def estimate_poses(points, lengths, start=None, search=OdometrySearch(), device=
             if cap is None:
                 longest = int(max(lengths))
                 n = int(np.sum(lengths)) if search.refresh is None else min(int(np.sum(lengths)), 2 * search.refresh * longest)
-                cap = mapping.MIN_FIRST_CAPACITY
-                while cap < 2 * (n // mapping.ROWS_PER_CELL_GUESS) and cap < ops.MAP_MAX_CAPACITY:
-                    cap *= 2
+                cap = mapping.first_capacity(n)
             for _ in range(mapping.MAX_DOUBLINGS + 1):
                 fields, counters, state = _run(rows, offsets, lengths, start, search, cap, dev)
                 c = torch.cat((counters.sum(dim=0), (S - state.sum(dtype=torch.int64)).reshape(1))).tolist()      # the wait

@@ -1577,12 +1577,7 @@ def drive_correct(poses, D, node_scan, node_pose, info=None):
         raise ValueError(f"drive_correct: node_pose must be [V, 12] = ({V}, 12), got {tuple(node_pose.shape)}")
     if len({poses.device, D.device, node_scan.device, node_pose.device}) != 1:
         raise ValueError("drive_correct: poses, D, node_scan and node_pose must be on one device")
-    if info is None:
-        info = _zeros((2,), torch.int32, poses.device)
-    else:
-        _req(info, "info", torch.int32)
-        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != poses.device:
-            raise ValueError(f"drive_correct: info must be a contiguous [2] int32 tensor on {poses.device}")
+    info = _counters("drive_correct", info, 2, torch.int32, poses.device)
     out = torch.empty((S, 12), dtype=torch.float64, device=poses.device)
     _call("drive_correct", _lib.load().lpd_drive_correct, _ptr(poses), _ptr(D.contiguous()), S, _ptr(node_scan.contiguous()),
           _ptr(node_pose.contiguous()), V, _ptr(out), _ptr(info), _stream())
@@ -1597,34 +1592,130 @@ def map_inv_cell(cell, what="map_insert"):
     if not MAP_MIN_CELL <= cell <= MAP_MAX_CELL:
         raise ValueError(f"{what}: cell={cell} m outside 2^-10 .. 16 (the bound that keeps every cell's sums inside an int64)")
     c32 = torch.tensor(cell, dtype=torch.float32)
-    inv = float(torch.tensor(1.0, dtype=torch.float32) / c32)
-    if not 1.0 / MAP_MAX_CELL <= inv <= 1.0 / MAP_MIN_CELL:
-        raise ValueError(f"{what}: cell={cell} m outside 2^-10 .. 16")
-    return inv
+    return _map_inv_cell(what, float(torch.tensor(1.0, dtype=torch.float32) / c32))      # in range: the rounded quotient is monotonic
 
 
-def _map_table(what, keys, acc, info):
+def map_capacity_ok(capacity):
+    """lpd_map_capacity_ok of csrc/lpd_map_math.h: a power of two in 16 .. 2^36"""
+    return MAP_MIN_CAPACITY <= capacity <= MAP_MAX_CAPACITY and not capacity & (capacity - 1)
+
+
+# ---- the stage's shared argument checks: one per concept, each naming the wrapper `what` it serves -------------------------------------
+def _map_keys(what, keys):
+    """keys [capacity] int64 of a voxel hash table, contiguous -> capacity (a power of two in 16 .. 2^36)"""
     _req(keys, "keys", torch.int64)
-    _req(acc, "acc", torch.int64)
-    _req(info, "info", torch.int64)
-    if keys is None or acc is None or info is None:
-        raise TypeError(f"{what}: keys, acc and info are tensors")
+    if keys is None:
+        raise TypeError(f"{what}: keys is a tensor")
     cap = keys.shape[0] if keys.dim() == 1 else 0
-    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
+    if not map_capacity_ok(cap) or not keys.is_contiguous():
         raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
-    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous():
-        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor, got {tuple(acc.shape)}")
-    if tuple(info.shape) != (4,) or not info.is_contiguous():
-        raise ValueError(f"{what}: info must be a contiguous [4] tensor, got {tuple(info.shape)}")
-    if not (keys.device == acc.device == info.device):
-        raise ValueError(f"{what}: keys, acc and info must be on one device")
     return cap
+
+
+def _map_rows(what, t, name, dtype, cap, width, device, aligned=False):
+    """a contiguous per-slot array of a table on `device`: acc [cap, 4], surf [cap, 8] and dirty [cap] (width None), these two aligned"""
+    _req(t, name, dtype)
+    if t is None:
+        raise TypeError(f"{what}: {name} is a tensor")
+    shape = (cap,) if width is None else (cap, width)
+    if tuple(t.shape) != shape or not t.is_contiguous() or t.device != device or (aligned and t.data_ptr() % 16):
+        raise ValueError(f"{what}: {name} must be a contiguous{', 16-byte aligned' if aligned else ''} [capacity{'' if width is None else f', {width}'}]"
+                         f" = {shape} {str(dtype)[6:]} tensor on {device}, got {tuple(t.shape)}")
+
+
+def _map_acc(what, acc, cap, device):
+    _map_rows(what, acc, "acc", torch.int64, cap, 4, device)
+
+
+def _map_surf(what, surf, cap, device):
+    _map_rows(what, surf, "surf", torch.float32, cap, LOC_SURF, device, aligned=True)
+
+
+def _map_dirty(what, dirty, cap, device):
+    if dirty is None:
+        raise ValueError(f"{what}: dirty must be a [capacity] = ({cap},) uint8 tensor")
+    _map_rows(what, dirty, "dirty", torch.uint8, cap, None, device, aligned=True)
+
+
+def _counters(what, info, n, dtype, device, name="info", make=True):
+    """the [n] counters that a call ADDS to: the caller's, or (make) new zeros"""
+    if info is None:
+        if not make:
+            raise TypeError(f"{what}: {name} is a tensor")
+        return _zeros((n,), dtype, device)
+    _req(info, name, dtype)
+    if tuple(info.shape) != (n,) or not info.is_contiguous() or info.device != device:
+        raise ValueError(f"{what}: {name} must be a contiguous [{n}] {str(dtype)[6:]} tensor on {device}")
+    return info
+
+
+def _map_table(what, keys, acc, info=None, counted=True):
+    """a table (keys, acc) and, where the call counts into it, its info [4] -> capacity"""
+    cap = _map_keys(what, keys)
+    _map_acc(what, acc, cap, keys.device)
+    if counted:
+        _counters(what, info, 4, torch.int64, keys.device, make=False)
+    return cap
+
+
+def _map_inv_cell(what, inv_cell):
+    inv_cell = float(inv_cell)
+    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
+        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    return inv_cell
+
+
+def _map_origin(what, origin, device):
+    _req(origin, "origin", torch.float64)
+    if origin is None:
+        raise TypeError(f"{what}: origin is a tensor")
+    if tuple(origin.shape) != (3,) or origin.device != device:
+        raise ValueError(f"{what}: origin must be [3] on {device}, got {tuple(origin.shape)} on {origin.device}")
+    return origin.contiguous()
+
+
+def _map_scan_range(what, scan0, scan1, S):
+    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
+    if not 0 <= scan0 < scan1 <= S:
+        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
+    return scan0, scan1
+
+
+def _map_two_tables(what, keys_in, acc_in, keys, acc):
+    """the table a copy reads (checked as keys / acc are) and the one it fills -> (capacity_in, capacity)"""
+    cap, cap_in = _map_table(what, keys, acc, counted=False), _map_table(what, keys_in, acc_in, counted=False)
+    if keys_in.device != keys.device:
+        raise ValueError(f"{what}: both tables must be on one device")
+    if keys_in.data_ptr() == keys.data_ptr() or acc_in.data_ptr() == acc.data_ptr():
+        raise ValueError(f"{what}: the new table must not be the old one")
+    return cap_in, cap
+
+
+class _PosedScans:
+    """What map_insert, map_touch and map_localize have in common, checked once.  table / scans / grid are the three runs of C arguments
+    that the entry points order differently around poses; the tensors behind the pointers live here."""
+    __slots__ = ("points", "offsets", "poses", "origin", "S", "cap", "table", "scans", "grid")
+
+    def __init__(self, what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1):
+        _req(points, "points")
+        self.poses, self.S = _drive_poses(what, poses)
+        if points is None:
+            raise TypeError(f"{what}: points is a tensor")
+        ld = _scan_points(what, points)
+        self.points, self.offsets = points, _drive_offsets(what, offsets, self.S)
+        self.cap = _map_keys(what, keys)
+        self.origin = _map_origin(what, origin, keys.device)
+        if len({points.device, self.offsets.device, self.poses.device, keys.device}) != 1:
+            raise ValueError(f"{what}: points, offsets, poses, origin and the table must be on one device")
+        self.table = (_ptr(points), ld, points.shape[0], _ptr(self.offsets))
+        self.scans = (self.S,) + _map_scan_range(what, scan0, scan1, self.S)
+        self.grid = (_ptr(self.origin), _map_inv_cell(what, inv_cell))
 
 
 def map_table(capacity, device):
     """An empty table for map_insert -> (keys [capacity] int64 = -1, acc [capacity, 4] int64 = 0, info [4] int64 = 0)"""
     capacity = int(capacity)
-    if not MAP_MIN_CAPACITY <= capacity <= MAP_MAX_CAPACITY or capacity & (capacity - 1):
+    if not map_capacity_ok(capacity):
         raise ValueError(f"map_table: capacity={capacity} is not a power of two in 16 .. 2^36")
     return (torch.full((capacity,), -1, dtype=torch.int64, device=device), torch.zeros((capacity, 4), dtype=torch.int64, device=device),
             torch.zeros((4,), dtype=torch.int64, device=device))
@@ -1636,40 +1727,17 @@ def map_insert(points, offsets, poses, origin, inv_cell, keys, acc, info, scan0=
     map_inv_cell(cell); keys / acc / info the caller's table (map_table), added to.  Nothing is read back: whether rows were lost is
     in info[2]."""
     what = "map_insert"
-    _req(points, "points")
-    _req(origin, "origin", torch.float64)
-    poses, S = _drive_poses(what, poses)
-    if points is None or origin is None:
-        raise TypeError(f"{what}: points and origin are tensors")
-    ld = _scan_points(what, points)
-    offsets = _drive_offsets(what, offsets, S)
-    if tuple(origin.shape) != (3,):
-        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
-    cap = _map_table(what, keys, acc, info)
-    if len({points.device, offsets.device, poses.device, origin.device, keys.device}) != 1:
-        raise ValueError(f"{what}: points, offsets, poses, origin and the table must be on one device")
-    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
-    if not 0 <= scan0 < scan1 <= S:
-        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
-    inv_cell = float(inv_cell)
-    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
-        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
-    _call("map_insert", _lib.load().lpd_map_insert, _ptr(points), ld, points.shape[0], _ptr(offsets), _ptr(poses), S, scan0, scan1,
-          _ptr(origin.contiguous()), inv_cell, _ptr(keys), _ptr(acc), cap, _ptr(info), _stream())
+    _map_table(what, keys, acc, info)
+    h = _PosedScans(what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1)
+    _call("map_insert", _lib.load().lpd_map_insert, *h.table, _ptr(h.poses), *h.scans, *h.grid, _ptr(keys), _ptr(acc), h.cap, _ptr(info), _stream())
 
 
 def map_rehash(keys_in, acc_in, keys, acc, info):
     """Every occupied slot of one table into another (lpd_map_rehash): how a table grows.  info [4] int64 of the new table is added to
     (rows = the cells' counts, cells created)."""
     what = "map_rehash"
-    _req(keys_in, "keys_in", torch.int64)
-    _req(acc_in, "acc_in", torch.int64)
-    cap = _map_table(what, keys, acc, info)
-    cap_in = _map_table(what, keys_in, acc_in, info)
-    if keys_in.device != keys.device:
-        raise ValueError(f"{what}: both tables must be on one device")
-    if keys_in.data_ptr() == keys.data_ptr() or acc_in.data_ptr() == acc.data_ptr():
-        raise ValueError(f"{what}: the new table must not be the old one")
+    cap_in, cap = _map_two_tables(what, keys_in, acc_in, keys, acc)
+    _counters(what, info, 4, torch.int64, keys.device, make=False)
     _call("map_rehash", _lib.load().lpd_map_rehash, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(keys), _ptr(acc), cap, _ptr(info), _stream())
 
 
@@ -1701,21 +1769,8 @@ def map_surface(keys, acc, reach=1, min_cells=5, info=None):
     read back."""
     what = "map_surface"
     reach, min_cells = map_surface_params(what, reach, min_cells)
-    _req(keys, "keys", torch.int64)
-    _req(acc, "acc", torch.int64)
-    if keys is None or acc is None:
-        raise TypeError(f"{what}: keys and acc are tensors")
-    cap = keys.shape[0] if keys.dim() == 1 else 0
-    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
-        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
-    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous() or acc.device != keys.device:
-        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor on {keys.device}, got {tuple(acc.shape)}")
-    if info is None:
-        info = _zeros((2,), torch.int64, keys.device)
-    else:
-        _req(info, "info", torch.int64)
-        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != keys.device:
-            raise ValueError(f"{what}: info must be a contiguous [2] int64 tensor on {keys.device}")
+    cap = _map_table(what, keys, acc, counted=False)
+    info = _counters(what, info, 2, torch.int64, keys.device)
     surf = torch.empty((cap, LOC_SURF), dtype=torch.float32, device=keys.device)
     _call("map_surface", _lib.load().lpd_map_surface, _ptr(keys), _ptr(acc), cap, reach, min_cells, _ptr(surf), _ptr(info), _stream())
     return surf, info
@@ -1747,30 +1802,9 @@ def map_localize(points, offsets, poses, origin, inv_cell, keys, surf, dmax, min
     outside the scans are 0), sums [iters + 1, S, 32] int64, cells [rows] int64 or None = the last pass's cell key of every row, -1
     without a correspondence).  Nothing is read back."""
     what = "map_localize"
-    _req(points, "points")
-    _req(origin, "origin", torch.float64)
-    _req(keys, "keys", torch.int64)
-    _req(surf, "surf")
-    poses, S = _drive_poses(what, poses)
-    if points is None or origin is None or keys is None or surf is None:
-        raise TypeError(f"{what}: points, origin, keys and surf are tensors")
-    ld = _scan_points(what, points)
-    offsets = _drive_offsets(what, offsets, S)
-    if tuple(origin.shape) != (3,):
-        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
-    cap = keys.shape[0] if keys.dim() == 1 else 0
-    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
-        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
-    if tuple(surf.shape) != (cap, LOC_SURF) or not surf.is_contiguous() or surf.data_ptr() % 16:
-        raise ValueError(f"{what}: surf must be a contiguous, 16-byte aligned [capacity, {LOC_SURF}] = ({cap}, {LOC_SURF}) tensor, got {tuple(surf.shape)}")
-    if len({points.device, offsets.device, poses.device, origin.device, keys.device, surf.device}) != 1:
-        raise ValueError(f"{what}: points, offsets, poses, origin and the map must be on one device")
-    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
-    if not 0 <= scan0 < scan1 <= S:
-        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
-    inv_cell = float(inv_cell)
-    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
-        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    h = _PosedScans(what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1)
+    _map_surf(what, surf, h.cap, keys.device)
+    S = h.S
     dm, iters = map_localize_dmax(what, dmax)
     if isinstance(min_inliers, bool) or not isinstance(min_inliers, numbers.Integral) or not LOC_MIN_INLIERS <= int(min_inliers) < 1 << 31:
         raise ValueError(f"{what}: min_inliers={min_inliers!r} (an integer >= {LOC_MIN_INLIERS})")
@@ -1781,14 +1815,13 @@ def map_localize(points, offsets, poses, origin, inv_cell, keys, surf, dmax, min
         raise ValueError(f"{what}: max_flat={max_flat!r} rounds to fp32 outside (0, 1]")
     lib = _lib.load()
     dev = points.device
-    pose = poses.clone()
+    pose = h.poses.clone()
     info = torch.zeros((S, 4), dtype=torch.int32, device=dev)
     sums = torch.empty((iters + 1, S, LOC_SUMS), dtype=torch.int64, device=dev)
     cells = torch.full((points.shape[0],), -1, dtype=torch.int64, device=dev) if want_cells else None
     ws = torch.empty((max(int(lib.lpd_map_localize_workspace_bytes(S, iters)), 16),), dtype=torch.uint8, device=dev)
-    _call("map_localize", lib.lpd_map_localize, _ptr(points), ld, points.shape[0], _ptr(offsets), S, scan0, scan1, _ptr(origin.contiguous()),
-          inv_cell, _ptr(keys), _ptr(surf), cap, dm, iters, int(min_inliers), max_flat32, _ptr(pose), _ptr(info), _ptr(sums), _ptr(cells),
-          _ptr(ws), _stream())
+    _call("map_localize", lib.lpd_map_localize, *h.table, *h.scans, *h.grid, _ptr(keys), _ptr(surf), h.cap, dm, iters, int(min_inliers), max_flat32,
+          _ptr(pose), _ptr(info), _ptr(sums), _ptr(cells), _ptr(ws), _stream())
     return pose, info, sums, cells
 
 
@@ -1884,33 +1917,24 @@ def map_crop(keys_in, acc_in, centre_pose, origin, inv_cell, keep_cells, keys, a
     centre_pose [12] float64 and origin [3] float64 on the device; info5 [5] int64 is added to (rows, -, rows lost, cells created, cells
     left behind).  A centre that is not finite keeps every cell.  Nothing is read back."""
     what = "map_crop"
-    _req(info5, "info5", torch.int64)
-    if info5 is None or tuple(info5.shape) != (5,) or not info5.is_contiguous():
+    if info5 is None:
         raise ValueError(f"{what}: info5 must be a contiguous [5] int64 tensor")
-    cap = _map_table(what, keys, acc, info5[:4])
-    cap_in = _map_table(what, keys_in, acc_in, info5[:4])
     _req(centre_pose, "centre_pose", torch.float64)
     _req(origin, "origin", torch.float64)
     if centre_pose is None or origin is None:
         raise TypeError(f"{what}: centre_pose and origin are tensors")
     if tuple(centre_pose.shape) != (12,) or not centre_pose.is_contiguous() or tuple(origin.shape) != (3,):
         raise ValueError(f"{what}: centre_pose must be a contiguous [12] and origin a [3] tensor, got {tuple(centre_pose.shape)} and {tuple(origin.shape)}")
-    if len({keys_in.device, keys.device, centre_pose.device, origin.device}) != 1:
+    cap_in, cap = _map_two_tables(what, keys_in, acc_in, keys, acc)
+    _counters(what, info5, 5, torch.int64, keys.device, "info5", make=False)
+    if centre_pose.device != keys.device:
         raise ValueError(f"{what}: both tables, centre_pose and origin must be on one device")
-    if keys_in.data_ptr() == keys.data_ptr() or acc_in.data_ptr() == acc.data_ptr():
-        raise ValueError(f"{what}: the new table must not be the old one")
-    inv_cell = float(inv_cell)
-    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
-        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    origin = _map_origin(what, origin, keys.device)
+    inv_cell = _map_inv_cell(what, inv_cell)
     keep_cells = _odom_whole(what, keep_cells, "keep_cells", 0, ODOM_MAX_KEEP_CELLS)
-    _call("map_crop", _lib.load().lpd_map_crop, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(centre_pose), _ptr(origin.contiguous()), inv_cell,
+    _call("map_crop", _lib.load().lpd_map_crop, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(centre_pose), _ptr(origin), inv_cell,
           keep_cells, _ptr(keys), _ptr(acc), cap, _ptr(info5), _stream())
 
-
-def _map_dirty(what, dirty, cap, device):
-    _req(dirty, "dirty", torch.uint8)
-    if dirty is None or tuple(dirty.shape) != (cap,) or not dirty.is_contiguous() or dirty.device != device or dirty.data_ptr() % 16:
-        raise ValueError(f"{what}: dirty must be a contiguous, 16-byte aligned [capacity] = ({cap},) uint8 tensor on {device}")
 
 
 def map_touch(points, offsets, poses, origin, inv_cell, keys, dirty, reach=1, scan0=0, scan1=None):
@@ -1918,31 +1942,10 @@ def map_touch(points, offsets, poses, origin, inv_cell, keys, dirty, reach=1, sc
     table after that insert, dirty [capacity] uint8 written IN PLACE (1 for every cell within `reach` of an inserted row's cell).
     Nothing is read back."""
     what = "map_touch"
-    _req(points, "points")
-    _req(origin, "origin", torch.float64)
-    _req(keys, "keys", torch.int64)
-    poses, S = _drive_poses(what, poses)
-    if points is None or origin is None or keys is None:
-        raise TypeError(f"{what}: points, origin and keys are tensors")
-    ld = _scan_points(what, points)
-    offsets = _drive_offsets(what, offsets, S)
-    if tuple(origin.shape) != (3,):
-        raise ValueError(f"{what}: origin must be [3], got {tuple(origin.shape)}")
-    cap = keys.shape[0] if keys.dim() == 1 else 0
-    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
-        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
-    _map_dirty(what, dirty, cap, keys.device)
-    if len({points.device, offsets.device, poses.device, origin.device, keys.device}) != 1:
-        raise ValueError(f"{what}: points, offsets, poses, origin and the table must be on one device")
-    scan0, scan1 = int(scan0), S if scan1 is None else int(scan1)
-    if not 0 <= scan0 < scan1 <= S:
-        raise ValueError(f"{what}: scans {scan0} .. {scan1} outside 0 .. {S} (at least one scan)")
-    inv_cell = float(inv_cell)
-    if not 1.0 / MAP_MAX_CELL <= inv_cell <= 1.0 / MAP_MIN_CELL:
-        raise ValueError(f"{what}: inv_cell={inv_cell} outside 1/16 .. 1024")
+    h = _PosedScans(what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1)
+    _map_dirty(what, dirty, h.cap, keys.device)
     reach, _ = map_surface_params(what, reach, LOC_MIN_CELLS)
-    _call("map_touch", _lib.load().lpd_map_touch, _ptr(points), ld, points.shape[0], _ptr(offsets), _ptr(poses), S, scan0, scan1,
-          _ptr(origin.contiguous()), inv_cell, _ptr(keys), cap, reach, _ptr(dirty), _stream())
+    _call("map_touch", _lib.load().lpd_map_touch, *h.table, _ptr(h.poses), *h.scans, *h.grid, _ptr(keys), h.cap, reach, _ptr(dirty), _stream())
 
 
 def map_surface_touched(keys, acc, surf, dirty, reach=1, min_cells=5, info=None):
@@ -1952,26 +1955,10 @@ def map_surface_touched(keys, acc, surf, dirty, reach=1, min_cells=5, info=None)
     the table bit for bit.  Nothing is read back."""
     what = "map_surface_touched"
     reach, min_cells = map_surface_params(what, reach, min_cells)
-    _req(keys, "keys", torch.int64)
-    _req(acc, "acc", torch.int64)
-    _req(surf, "surf")
-    if keys is None or acc is None or surf is None:
-        raise TypeError(f"{what}: keys, acc and surf are tensors")
-    cap = keys.shape[0] if keys.dim() == 1 else 0
-    if not MAP_MIN_CAPACITY <= cap <= MAP_MAX_CAPACITY or cap & (cap - 1) or not keys.is_contiguous():
-        raise ValueError(f"{what}: keys must be a contiguous [capacity] tensor, capacity a power of two in 16 .. 2^36, got {tuple(keys.shape)}")
-    if tuple(acc.shape) != (cap, 4) or not acc.is_contiguous() or acc.device != keys.device:
-        raise ValueError(f"{what}: acc must be a contiguous [capacity, 4] = ({cap}, 4) tensor on {keys.device}, got {tuple(acc.shape)}")
-    if tuple(surf.shape) != (cap, LOC_SURF) or not surf.is_contiguous() or surf.data_ptr() % 16 or surf.device != keys.device:
-        raise ValueError(f"{what}: surf must be a contiguous, 16-byte aligned [capacity, {LOC_SURF}] = ({cap}, {LOC_SURF}) tensor on {keys.device}, "
-                         f"got {tuple(surf.shape)}")
+    cap = _map_table(what, keys, acc, counted=False)
+    _map_surf(what, surf, cap, keys.device)
     _map_dirty(what, dirty, cap, keys.device)
-    if info is None:
-        info = _zeros((2,), torch.int64, keys.device)
-    else:
-        _req(info, "info", torch.int64)
-        if tuple(info.shape) != (2,) or not info.is_contiguous() or info.device != keys.device:
-            raise ValueError(f"{what}: info must be a contiguous [2] int64 tensor on {keys.device}")
+    info = _counters(what, info, 2, torch.int64, keys.device)
     _call("map_surface_touched", _lib.load().lpd_map_surface_touched, _ptr(keys), _ptr(acc), cap, reach, min_cells, _ptr(surf), _ptr(dirty),
           _ptr(info), _stream())
     return info

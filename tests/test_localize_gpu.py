@@ -283,6 +283,40 @@ def test_a_sub_range_of_scans_leaves_the_others_bit_for_bit(cuda):
     assert got["info"][1].tolist()[:3] == [1, 2, 0] and np.abs(got["pose"][1] - start[1]).max() > 1e-3
 
 
+def test_a_broken_offsets_table_is_not_read(cuda):
+    """48 scans of 64 rows: the scans 16 .. 31 are exactly the second chunk, and offsets[20] = offsets[21] + 5 descends inside it.  That
+    chunk alone is refused -- its rows get no correspondence, its scans no step -- and every other scan comes out as on the intact
+    table: 1349 and 1280 lie on the same side of every row of the other chunks, so the binary search answers there as before."""
+    S, n, iters = 48, 64, 2
+    mp, table, surf, want = _std(cuda)
+    pts, off, start = _query_case(21, [n] * S)
+    bad = off.copy()
+    bad[20] = bad[21] + 5
+    second = np.arange(M.CHUNK, 2 * M.CHUNK)
+    # the chunk rule of the restatement: the second chunk is not read, every other row is, by the scan it belongs to
+    g, scan, not_read = M.row_scans(bad, 0, S, S * n)
+    assert not_read == M.CHUNK and np.array_equal(g, np.delete(np.arange(S * n), second)) and np.array_equal(scan, g // n)
+    whole = _ref("broken: intact", lambda: L.localize(want, pts, off, start, mp[3], 1.0, DMAX3, 6))
+    assert (whole["info"][:, 1] == iters).all() and whole["info"][:, 3].min() > 6
+    got = _localize(cuda, table, surf, pts, bad, start, mp[3], 1.0, DMAX3, 6)
+    others = np.r_[0:16, 32:S]
+    for k in ("pose", "info"):
+        assert got[k][others].tobytes() == whole[k][others].tobytes(), k
+    assert np.array_equal(got["sums"][:, others], whole["sums"][:, others])
+    assert got["info"][20, 0] == -1
+    for i in range(16, 32):
+        assert i == 20 or got["info"][i].tolist() == [1, 0, iters, 0], (i, got["info"][i])
+        assert not got["sums"][:, i].any() and got["pose"][i].tobytes() == start[i].tobytes(), i
+    assert (got["cell"][second] == -1).all()
+    assert np.array_equal(np.delete(got["cell"], second), np.delete(whole["cell"], second))
+    _check(got, _ref("broken", lambda: L.localize(want, pts, bad, start, mp[3], 1.0, DMAX3, 6)), "the restatement on the broken table")
+    for lo, hi in ((0, S * n + 1), (-1, S * n), (200, 100)):      # the call reads nothing
+        worse = off.copy()
+        worse[0], worse[-1] = lo, hi
+        got = _localize(cuda, table, surf, pts, worse, start, mp[3], 1.0, DMAX3, 6)
+        assert got["pose"].tobytes() == start.tobytes() and not got["sums"].any() and (got["cell"] == -1).all(), (lo, hi)
+
+
 def test_nan_rows_a_nan_pose_and_a_scan_of_more_than_2_to_20_rows(cuda):
     mp, table, surf, want = _std(cuda)
     pts, off, start = _query_case(14, [400, 600, 500])

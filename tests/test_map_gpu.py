@@ -377,6 +377,33 @@ def test_argument_errors_name_their_function(cuda):
         mapping.correct_scan_poses(plan, plan.poses, p)
     with pytest.raises(TypeError, match="correct_scan_poses: result"):
         mapping.correct_scan_poses(plan, plan.poses, p.float())
+    # every wrapper of the map and its localisation through every check they share: ONE wrong argument a call, the exception and the
+    # words "<wrapper>: <argument>" (tests/test_odometry_gpu.py has the table of map_crop, map_touch and map_surface_touched)
+    k2, a2, _ = ops.map_table(32, cuda)
+    surf = torch.zeros((16, 8), device=cuda)
+    surf_off = torch.zeros((16 * 8 + 1,), device=cuda)[1:].view(16, 8)      # one float off a 16-byte boundary
+    assert surf_off.is_contiguous() and surf_off.data_ptr() % 16 == 4
+    good = dict(drive_correct=dict(poses=p, D=D, node_scan=ns, node_pose=p[:1]),
+                map_insert=dict(points=pts, offsets=off, poses=p, origin=org, inv_cell=1.0, keys=keys, acc=acc, info=info),
+                map_rehash=dict(keys_in=k2, acc_in=a2, keys=keys, acc=acc, info=info),
+                map_surface=dict(keys=keys, acc=acc),
+                map_localize=dict(points=pts, offsets=off, poses=p, origin=org, inv_cell=1.0, keys=keys, surf=surf, dmax=(1.0, 1.0)))
+    wrong = [("map_insert", dict(keys=keys[:12]), "keys"), ("map_rehash", dict(keys=keys[:12]), "keys"), ("map_rehash", dict(keys_in=k2[:12]), "keys"),
+             ("map_surface", dict(keys=keys[:12]), "keys"), ("map_localize", dict(keys=keys[:12]), "keys"),
+             ("map_insert", dict(acc=acc[:, :3]), "acc"), ("map_rehash", dict(acc=acc[:, :3]), "acc"), ("map_rehash", dict(acc_in=a2[:, :3]), "acc"),
+             ("map_surface", dict(acc=acc[:, :3]), "acc"),
+             ("map_localize", dict(surf=surf_off), "surf"),
+             ("map_insert", dict(scan0=2, scan1=2), "scans"), ("map_localize", dict(scan0=2, scan1=2), "scans"),
+             ("map_insert", dict(inv_cell=4096.0), "inv_cell"), ("map_localize", dict(inv_cell=4096.0), "inv_cell"),
+             ("map_insert", dict(origin=org[:2]), "origin"), ("map_localize", dict(origin=org[:2]), "origin"),
+             ("map_rehash", dict(keys_in=keys, acc_in=acc), "the new table"),
+             ("drive_correct", dict(info=torch.zeros(3, dtype=torch.int32, device=cuda)), "info"), ("map_insert", dict(info=info[:3]), "info"),
+             ("map_rehash", dict(info=info[:3]), "info"), ("map_surface", dict(info=torch.zeros(3, dtype=torch.int64, device=cuda)), "info")]
+    for name, args in good.items():
+        getattr(ops, name)(**args)      # the table's calls are good ones but for the one argument
+    for name, bad, arg in wrong:
+        with pytest.raises(ValueError, match=f"{name}: {arg}"):
+            getattr(ops, name)(**dict(good[name], **bad))
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------------------------

@@ -172,6 +172,39 @@ def test_crop_into_a_table_that_is_too_small_counts_the_lost_rows(cuda):
     assert c[0] + c[2] == len(pts) and c[2] > 0 and c[3] == 16 and c[4] == 0
 
 
+def test_rehash_and_crop_are_one_copy(cuda):
+    """600 cells in 2^10 slots into 2^11 slots by lpd_map_rehash, by a crop around a centre that is not finite and by a crop that keeps
+    more cells than the map is wide: the same cells bit for bit and the same first four counters.  Into 16 slots WHICH keys are lost
+    depends on timing; that the counters add up does not."""
+    from lpdnet_hip import mapping, ops
+    pts = _cell_rows(8, 600, 6)
+    table = _insert(cuda, pts, 1 << 10)
+    assert table[2].tolist() == [len(pts), 0, 0, 600]
+    nan = CENTRE.copy()
+    nan[5] = np.nan
+
+    def rehash(capacity):
+        keys, acc, info = ops.map_table(capacity, cuda)
+        ops.map_rehash(table[0], table[1], keys, acc, info)
+        return keys, acc, info, None
+
+    def three_ways(capacity):
+        return rehash(capacity), _crop(cuda, table, nan, 0, capacity), _crop(cuda, table, CENTRE, 64, capacity)
+    outs = []
+    for keys, acc, info, info5 in three_ways(1 << 11):
+        c = mapping.extract_cells(keys, acc, None, 1.0)
+        outs.append([x.cpu().numpy().tobytes() for x in (c.keys, c.counts, c.sums, c.points)] + [info.tolist()])
+        assert info.tolist() == [len(pts), 0, 0, 600]
+        assert info5 is None or int(info5[4]) == 0
+    assert outs[0] == outs[1] == outs[2]
+    want = mapping.extract_cells(table[0], table[1], None, 1.0)
+    assert outs[0][0] == want.keys.cpu().numpy().tobytes() and outs[0][2] == want.sums.cpu().numpy().tobytes()
+    for keys, acc, info, info5 in three_ways(16):
+        c, occupied = info.tolist(), int((keys >= 0).sum())
+        assert c[0] + c[2] == len(pts) and c[1] == 0 and c[3] == occupied <= 16, c
+        assert int(acc[:, 3].sum()) == c[0] and (info5 is None or int(info5[4]) == 0)
+
+
 # ---- touch + refresh against the full surface ----------------------------------------------------------------------------------------------------------
 def _scan_rows(rng, n, box, z=2.0):
     """n rows in [-box, box]^2 x [0, z): most on a floor and a wall, so that cells get normals"""
@@ -437,6 +470,28 @@ def test_wrappers_refuse_bad_arguments(cuda):
             bad()
     with pytest.raises(TypeError):
         ops.map_touch(pts, poff, P[:1], origin, 1.0, keys, dirty.to(torch.int32))
+    # the three wrappers of this file through every check they share with the map's (tests/test_map_gpu.py has the others): ONE wrong
+    # argument a call, the exception and the words "<wrapper>: <argument>".  map_crop names a wrong origin under centre_pose's message.
+    surf_off = torch.zeros((64 * 8 + 1,), device=cuda)[1:].view(64, 8)      # one float off a 16-byte boundary
+    assert surf_off.is_contiguous() and surf_off.data_ptr() % 16 == 4
+    good = dict(map_crop=dict(keys_in=keys, acc_in=acc, centre_pose=centre, origin=origin, inv_cell=1.0, keep_cells=1, keys=k2, acc=a2, info5=i2),
+                map_touch=dict(points=pts, offsets=poff, poses=P[:1], origin=origin, inv_cell=1.0, keys=keys, dirty=dirty),
+                map_surface_touched=dict(keys=keys, acc=acc, surf=surf, dirty=dirty))
+    wrong = [("map_crop", dict(keys=k2[:12]), "keys"), ("map_crop", dict(keys_in=keys[:48]), "keys"), ("map_touch", dict(keys=keys[:48]), "keys"),
+             ("map_surface_touched", dict(keys=keys[:48]), "keys"),
+             ("map_crop", dict(acc=a2[:, :3]), "acc"), ("map_crop", dict(acc_in=acc[:, :3]), "acc"), ("map_surface_touched", dict(acc=acc[:, :3]), "acc"),
+             ("map_surface_touched", dict(surf=surf_off), "surf"),
+             ("map_touch", dict(dirty=dirty[:32]), "dirty"), ("map_surface_touched", dict(dirty=dirty[:32]), "dirty"),
+             ("map_touch", dict(scan0=1, scan1=1), "scans"),
+             ("map_crop", dict(inv_cell=4096.0), "inv_cell"), ("map_touch", dict(inv_cell=4096.0), "inv_cell"),
+             ("map_crop", dict(origin=origin[:2]), "centre_pose"), ("map_touch", dict(origin=origin[:2]), "origin"),
+             ("map_crop", dict(keys=keys, acc=acc), "the new table"),
+             ("map_crop", dict(info5=i2[:4]), "info5"), ("map_surface_touched", dict(info=torch.zeros(3, dtype=torch.int64, device=cuda)), "info")]
+    for name, args in good.items():
+        getattr(ops, name)(**args)      # the table's calls are good ones but for the one argument
+    for name, bad, arg in wrong:
+        with pytest.raises(ValueError, match=f"{name}: {arg}"):
+            getattr(ops, name)(**dict(good[name], **bad))
     with pytest.raises(ValueError):
         odometry.estimate_poses([torch.zeros((0, 3), device=cuda)], None)
     with pytest.raises(ValueError):
