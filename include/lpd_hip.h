@@ -1119,6 +1119,48 @@ int lpd_map_touch(const float* points, int ld, int rows, const int32_t* offsets,
 int lpd_map_surface_touched(const long long* keys, const long long* acc, long long capacity, int reach, int min_cells, float* surf,
                             unsigned char* dirty, long long* info, void* stream);
 
+/*
+ * Motion compensation of LiDAR sweeps (csrc/lpd_deskew.hip, lpd_odom_motion in csrc/lpd_odom.hip; arithmetic in
+ * csrc/lpd_deskew_math.h).  A spinning LiDAR measures the rows of one scan over the whole period of its sweep while the sensor moves;
+ * every stage above takes a scan as a rigid snapshot.  lpd_scan_deskew brings every row into the frame the sensor had at ONE time of
+ * the sweep, from the time of the row and the motion of the sensor during the sweep -- the first step of KISS-ICP, which takes the
+ * motion from the constant-velocity model.  This comment is the specification, and lpd_deskew_math.h settles every detail it leaves
+ * open.  Float64 with + - * / sqrt only, every operation rounded once, nothing contracted; integer atomics only; no barrier across
+ * workgroups; no read-back; the same bits in every launch.
+ *
+ * Inputs.  times [rows] fp32, one value a row of the scan table with the row numbering of points: the fraction of the scan's period
+ * at which the row was measured, 0 .. 1.  motion [S][12] float64, one rigid motion a scan, row-major 3 x 4: the pose of the sensor at
+ * the END of the period in the frame of its START.  ref, a double in 0 .. 1: the time whose frame the scan is brought into (0.5 is
+ * KISS-ICP's choice: the middle of the sweep).
+ *
+ *  1 Row.      a = (double) times[g] - ref; the row (x, y, z) becomes R_a (x, y, z) + a t, where (R_a | a t) =
+ *              lpd_map_blend(identity, motion_i, a) of lpd_map_math.h IN EVERY BIT: the normalised blend of the two quaternions and the
+ *              linear blend of the translations that lpd_drive_correct uses -- the repository's one definition of a blended pose.  The
+ *              three coordinates are float64 dot products in the order of lpd_drive_coord, (((m0 x) + (m1 y)) + (m2 z)) + u, each
+ *              rounded to fp32 ONCE.  Under the identity motion the result compares equal to the input.
+ *  2 Scan.     What of the blend depends on the scan alone (the motion's quaternion by lpd_pgo_quat, its sign chosen against the
+ *              identity's (1, 0, 0, 0), the differences to the identity) is made once a chunk (LpdDeskewScan); a row costs one square
+ *              root and four divisions.
+ *  3 Passed.   A row whose time does not lie in 0 .. 1 (a NaN does not, -0.0 does) or whose scan's motion holds a value that is not
+ *              finite is written as a bit copy of its input and counted in info[1]; info[0] counts the transformed rows.  info [2]
+ *              int64, ADDED to, one integer atomic a wave and counter.
+ *  4 Walk.     The rows of the scans scan0 .. scan1-1 in chunks of 1024, exactly as lpd_map_insert walks them (rule 5 there): a
+ *              chunk that a broken offsets table refuses is neither read nor written nor counted, and nothing outside [0, rows) and
+ *              [scan0, scan1] is touched whatever offsets holds.  Rows outside the scans are not written.
+ * out [rows][3] fp32, rows contiguous; out may be points itself when ld == 3 (a chunk reads its rows before it writes them).
+ *
+ * lpd_drive_motions.  poses [S][12] float64 -> motion [S][12] float64 (not poses), one thread a scan: motion[i] =
+ * lpd_pgo_between(poses[i], poses[i+1]) packed as a pose; the last scan repeats the motion before it; S == 1 gives the identity.  A pose
+ * that is not finite gives a motion that is not finite, whose rows rule 3 passes through and counts.
+ *
+ * lpd_odom_motion.  One thread, beside lpd_odom_predict: motion[t] = lpd_pgo_between(pose[t-2], pose[t-1]) for t >= 2 -- the motion
+ * the constant-velocity start assumes; for t < 2 first_motion [12] (on the device) as it is, the identity when that is NULL.
+ */
+int lpd_scan_deskew(const float* points, int ld, int rows, const int32_t* offsets, const float* times, const double* motion, int S, int scan0,
+                    int scan1, double ref, float* out, long long* info, void* stream);
+int lpd_drive_motions(const double* poses, int S, double* motion, void* stream);
+int lpd_odom_motion(const double* pose, int S, int t, const double* first_motion, double* motion, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

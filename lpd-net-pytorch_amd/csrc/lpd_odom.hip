@@ -2,6 +2,8 @@
 // scan-to-local-map odometry that never waits for the host.  Definition: include/lpd_hip.h; arithmetic: lpd_odom_math.h.
 //
 //   predict  one thread: the constant-velocity start of scan t from the two poses before it, into pred [t] and pose [t].
+//   motion   one thread: the motion of the sensor during scan t under the same model, into motion [t] -- what lpd_scan_deskew
+//            (lpd_deskew.hip) takes for that scan (lpd_deskew_math.h).
 //   accept   one thread: the decision on scan t after its localisation; a refused scan keeps its prediction and gets a NaN insert pose.
 //   (crop    lpd_map_crop is the table-to-table copy of lpd_map.hip with the predicate of lpd_odom_math.h; its entry point is there.)
 //   touch    grid = the chunks of LPD_MAP_CHUNK = 1024 input rows, OD_T = 256 threads, the chunk found, checked and staged by the
@@ -16,6 +18,7 @@
 #include <math.h>
 
 #include "lpd_common.h"
+#include "lpd_deskew_math.h"
 #include "lpd_map_table.h"
 #include "lpd_odom_math.h"
 #include "lpd_scan_chunk.h"
@@ -37,6 +40,15 @@ __global__ __launch_bounds__(64) void predict_kernel(double* __restrict__ pose, 
     double o[12];
     lpd_odom_predict_pose(pose, t, first_motion, o);
     for (int k = 0; k < 12; ++k) pred[(size_t)12 * t + k] = pose[(size_t)12 * t + k] = o[k];
+}
+
+__global__ __launch_bounds__(64) void motion_kernel(const double* __restrict__ pose, int t, const double* __restrict__ first_motion,
+                                                    double* __restrict__ motion)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double o[12];
+    lpd_deskew_odom_motion(pose, t, first_motion, o);
+    for (int k = 0; k < 12; ++k) motion[(size_t)12 * t + k] = o[k];
 }
 
 __global__ __launch_bounds__(64) void accept_kernel(const double* __restrict__ pred, double* __restrict__ pose, const int32_t* __restrict__ info,
@@ -153,6 +165,18 @@ extern "C" int lpd_odom_predict(double* pose, double* pred, int S, int t, const 
     LPD_CHECK_ARG((const void*)pose != (const void*)pred, "lpd_odom_predict: pred must not be pose");
     hipLaunchKernelGGL(predict_kernel, dim3(1), dim3(64), 0, stream, pose, pred, t, first_motion);
     LPD_CHECK_LAUNCH("lpd_odom_predict");
+    return LPD_OK;
+}
+
+extern "C" int lpd_odom_motion(const double* pose, int S, int t, const double* first_motion, double* motion, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    LPD_CHECK_ARG(pose && motion, "lpd_odom_motion: null pointer");
+    LPD_CHECK_ARG(S >= 1 && S <= LPD_DRIVE_MAX_SCANS, "lpd_odom_motion: S=%d outside 1 .. 2^22", S);
+    LPD_CHECK_ARG(t >= 0 && t < S, "lpd_odom_motion: t=%d outside 0 .. S-1=%d", t, S - 1);
+    LPD_CHECK_ARG((const void*)pose != (const void*)motion, "lpd_odom_motion: motion must not be pose");
+    hipLaunchKernelGGL(motion_kernel, dim3(1), dim3(64), 0, stream, pose, t, first_motion, motion);
+    LPD_CHECK_LAUNCH("lpd_odom_motion");
     return LPD_OK;
 }
 

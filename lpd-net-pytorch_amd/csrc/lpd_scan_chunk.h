@@ -1,7 +1,7 @@
 // lpd_scan_chunk.h -- one workgroup stages a chunk of the ragged scan table (points [rows][ld], offsets [S+1], one pose a scan): the
-// steps that rows_kernel (lpd_drive.hip), insert_kernel (lpd_map.hip), touch_kernel (lpd_odom.hip) and loc_pass_kernel
-// (lpd_localize.hip) share.  HIP only.  A chunk is cn <= CH consecutive rows of the table from row g0 on, which belong to the
-// consecutive scans i_lo .. i_hi.  LpdScanChunk<T, CH, CAP> serves a workgroup of T threads that keeps CAP poses; the LDS arrays (buf
+// steps that rows_kernel (lpd_drive.hip), insert_kernel (lpd_map.hip), touch_kernel (lpd_odom.hip), loc_pass_kernel
+// (lpd_localize.hip) and deskew_kernel (lpd_deskew.hip, whose "pose" of a scan is the per-scan part of its motion) share.  HIP only.
+// A chunk is cn <= CH consecutive rows of the table from row g0 on, which belong to the consecutive scans i_lo .. i_hi.  LpdScanChunk<T, CH, CAP> serves a workgroup of T threads that keeps CAP poses; the LDS arrays (buf
 // [3 CH], rel [CAP], soff [CAP + 1], span [2]) are the kernel's and come in as pointers.  Nothing here knows which kernel calls it, what
 // a pose is relative to, or what becomes of a row.
 //
@@ -121,10 +121,10 @@ struct LpdScanChunk {
         return !__syncthreads_or(bad);
     }
 
-    // pose(i) -> LpdDriveRel of scan i.  Reads offsets[i_lo .. i_lo + ns]: i_lo + ns = i_hi + 1 <= S
-    template <class P>
-    static __device__ __forceinline__ bool poses(const int32_t* __restrict__ offsets, int i_lo, int ns, LpdDriveRel* rel, int32_t* soff, int tid,
-                                                 P&& pose)
+    // pose(i) -> the record of scan i: an LpdDriveRel, or what else a kernel makes once a scan (Rec is the type of its LDS table).
+    // Reads offsets[i_lo .. i_lo + ns]: i_lo + ns = i_hi + 1 <= S
+    template <class Rec, class P>
+    static __device__ __forceinline__ bool poses(const int32_t* __restrict__ offsets, int i_lo, int ns, Rec* rel, int32_t* soff, int tid, P&& pose)
     {
         if (ns > CAP) return false;
         if (tid < ns) rel[tid] = pose(i_lo + tid);
@@ -132,9 +132,9 @@ struct LpdScanChunk {
         return true;
     }
 
-    template <class P>
-    static __device__ __forceinline__ LpdDriveRel row_pose(bool table, const LpdDriveRel* rel, const int32_t* soff,
-                                                           const int32_t* __restrict__ offsets, int i_lo, int ns, long long g, P&& pose)
+    template <class Rec, class P>
+    static __device__ __forceinline__ Rec row_pose(bool table, const Rec* rel, const int32_t* soff, const int32_t* __restrict__ offsets, int i_lo,
+                                                   int ns, long long g, P&& pose)
     {
         if (table) return rel[lpd_drive_scan_of(soff, 0, ns, g)];
         return pose(lpd_drive_scan_of(offsets, i_lo, i_lo + ns, g));

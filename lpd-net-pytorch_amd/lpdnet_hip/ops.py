@@ -1964,6 +1964,79 @@ def map_surface_touched(keys, acc, surf, dirty, reach=1, min_cells=5, info=None)
     return info
 
 
+# motion compensation of LiDAR sweeps (csrc/lpd_deskew.hip, lpd_odom_motion in csrc/lpd_odom.hip)
+def deskew_ref(ref, what="scan_deskew"):
+    """the reference time of a sweep, a real number in 0 .. 1 -> float"""
+    if isinstance(ref, bool) or not isinstance(ref, numbers.Real) or not 0.0 <= float(ref) <= 1.0:
+        raise ValueError(f"{what}: ref={ref!r} outside 0 .. 1")
+    return float(ref)
+
+
+def scan_deskew(points, offsets, times, motion, ref=0.5, out=None, info=None, scan0=0, scan1=None):
+    """The rows of the scans scan0 .. scan1-1 brought into the frame their sweep had at the time `ref` (lpd_scan_deskew; definition in
+    include/lpd_hip.h): points [rows, >=3] fp32 with contiguous rows, offsets [S+1] int32, times [rows] fp32 = the fraction of its
+    scan's period at which a row was measured, motion [S, 12] float64 = the sensor's pose at the end of the period in the frame of its
+    start, all on the device.  out: a contiguous [rows, 3] fp32 tensor written IN PLACE (rows outside the scans are not touched), zeros
+    when None; it may be points itself when that is contiguous [rows, 3].  info [2] int64 is added to (rows transformed, rows passed
+    through as they are: a time outside 0 .. 1 or a motion that is not finite).  -> (out, info).  Nothing is read back."""
+    what = "scan_deskew"
+    _req(points, "points")
+    motion, S = _drive_poses(what, motion)
+    if points is None:
+        raise TypeError(f"{what}: points is a tensor")
+    ld = _scan_points(what, points)
+    rows = points.shape[0]
+    offsets = _drive_offsets(what, offsets, S)
+    _req(times, "times")
+    if times is None:
+        raise TypeError(f"{what}: times is a tensor")
+    if tuple(times.shape) != (rows,) or not times.is_contiguous():
+        raise ValueError(f"{what}: times must be a contiguous [rows] = ({rows},) tensor, got {tuple(times.shape)}")
+    if out is None:
+        out = _zeros((rows, 3), torch.float32, points.device)
+    _req(out, "out")
+    if tuple(out.shape) != (rows, 3) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous [rows, 3] = ({rows}, 3) tensor, got {tuple(out.shape)}")
+    if out.data_ptr() == points.data_ptr():
+        if ld != 3:
+            raise ValueError(f"{what}: out may be points only when its rows are three floats apart (ld = {ld})")
+    elif out.data_ptr() < points.data_ptr() + 4 * ((rows - 1) * ld + 3) and points.data_ptr() < out.data_ptr() + 12 * rows:
+        raise ValueError(f"{what}: out overlaps points without being points")
+    info = _counters(what, info, 2, torch.int64, points.device)
+    if len({points.device, offsets.device, times.device, motion.device, out.device}) != 1:
+        raise ValueError(f"{what}: points, offsets, times, motion and out must be on one device")
+    scan0, scan1 = _map_scan_range(what, scan0, scan1, S)
+    _call("scan_deskew", _lib.load().lpd_scan_deskew, _ptr(points), ld, rows, _ptr(offsets), _ptr(times), _ptr(motion), S, scan0, scan1,
+          deskew_ref(ref, what), _ptr(out), _ptr(info), _stream())
+    return out, info
+
+
+def drive_motions(poses):
+    """The motion of the sensor during every scan of a posed drive (lpd_drive_motions): poses [S, 12] float64 on the device -> motion
+    [S, 12] float64, motion[i] = poses[i]^-1 poses[i+1]; the last scan repeats the motion before it, one scan alone gets the identity.
+    Nothing is read back."""
+    poses, S = _drive_poses("drive_motions", poses)
+    motion = torch.empty((S, 12), dtype=torch.float64, device=poses.device)
+    _call("drive_motions", _lib.load().lpd_drive_motions, _ptr(poses), S, _ptr(motion), _stream())
+    return motion
+
+
+def odom_motion(pose, t, motion, first_motion=None):
+    """The motion of the sensor during scan t of the odometry (lpd_odom_motion): pose, motion [S, 12] float64 on the device, motion[t]
+    written IN PLACE -- pose[t-2]^-1 pose[t-1] for t >= 2, first_motion [12] float64 on the device (the identity when None) before.
+    Nothing is read back."""
+    what = "odom_motion"
+    S = _odom_poses(what, (("pose", pose), ("motion", motion)))
+    if pose.data_ptr() == motion.data_ptr():
+        raise ValueError(f"{what}: motion must not be pose")
+    t = _odom_whole(what, t, "t", 0, S - 1)
+    if first_motion is not None:
+        _req(first_motion, "first_motion", torch.float64)
+        if tuple(first_motion.shape) != (12,) or not first_motion.is_contiguous() or first_motion.device != pose.device:
+            raise ValueError(f"{what}: first_motion must be a contiguous [12] tensor on {pose.device}, got {tuple(first_motion.shape)}")
+    _call("odom_motion", _lib.load().lpd_odom_motion, _ptr(pose), S, t, _ptr(first_motion), _ptr(motion), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # geometric verification of retrieved places (csrc/lpd_align.hip)
 # ------------------------------------------------------------------------------------------------
