@@ -1161,6 +1161,76 @@ int lpd_scan_deskew(const float* points, int ld, int rows, const int32_t* offset
 int lpd_drive_motions(const double* poses, int S, double* motion, void* stream);
 int lpd_odom_motion(const double* pose, int S, int t, const double* first_motion, double* motion, void* stream);
 
+/*
+ * Moving objects out of the drive map (csrc/lpd_carve.hip; arithmetic in csrc/lpd_carve_math.h).  Every stage above assumes a static
+ * world; a car that drives through the scene leaves a trail of cells in the table.  Every row of the scan table is a ray from a known
+ * sensor position, and a cell that many later rays pass straight through was not a wall.  lpd_map_pierce counts those rays per occupied
+ * cell, lpd_map_carve copies the table without the cells that were pierced often enough, lpd_scan_moving marks the input rows that lie in
+ * such a cell.  This comment is the specification, and lpd_carve_math.h settles every detail it leaves open.  The stage never inserts
+ * into the table it reads and reads keys, acc and surf only; integer atomics only; no barrier across workgroups; no read-back; every
+ * address that comes from data is masked or checked first.  A count belongs to a KEY, not to the slot the key landed in: per key the
+ * result is the same bits in every launch, at every capacity, under any batching of scans and on any stream.
+ *
+ * lpd_map_pierce.  points / ld / rows / offsets / poses / S / scan0 / scan1 / origin / inv_cell / keys / capacity as lpd_map_localize
+ * takes them; surf [capacity][8] from lpd_map_surface, 16-byte aligned.
+ *   pierce     [capacity] int32, ADDED to: one a ray and pierced cell, at the cell's slot
+ *   info       [6] int64, ADDED to: rays traversed, rows dropped, rays cut at max_steps, cells stepped into, cells found, pierces counted
+ *   skip_end, skip_start   0 .. 16 cells;  max_steps 1 .. 8192;  max_flat in (0, 1];  clearance, radius in metres, finite, > 0
+ *  1 Walk.     The rows are walked as lpd_map_insert walks them (rule 5 there, chunks of 1024); a chunk that is not read counts its rows
+ *              as dropped.
+ *  2 Ray.      r = lpd_map_rel(pose, origin), the insert's; the endpoint w is the insert's world row, the sensor o = r.u in fp32.  A row
+ *              whose endpoint has no cell (lpd_map_index) is dropped; so is every row of a scan whose o has no cell or whose pose is
+ *              not finite.
+ *  3 Units.    Per axis f = w_c * inv_cell and e = o_c * inv_cell, one fp32 product each -- the product lpd_map_index floors.
+ *              A_c = 2 (int64) floor((double) f * 256.0) + 1, B_c likewise from e: units of 1/512 cell, always odd; cell walls are the
+ *              multiples of 512, so a point never lies on a wall, and A_c >> 9 == (int) floorf(f).
+ *  4 Steps.    D = A - B, s_c = sign(D_c), n = sum |qa_c - qb_c| (qa, qb the cells of A, B).  The next wall of axis c is W_c =
+ *              512 (q_c + (s_c > 0)), N_c = |W_c - B_c|.  Each step takes the axis with the smallest N_c / |D_c|, compared by cross-
+ *              multiplication N_i |D_j| < N_j |D_i| (both factors below 2^31); ties go to the lowest axis; an axis with D_c == 0 is
+ *              never taken.  After a step on axis c: q_c += s_c, N_c += 512.  Exact: no floating point after rule 3.
+ *  5 Visits.   The cells visited are those after steps 1 .. min(n - 1, max_steps): neither the sensor's cell nor the endpoint's.  A ray
+ *              with n - 1 > max_steps is counted in info[2].  A visited cell nearer than skip_end cells (Chebyshev) to the endpoint's
+ *              cell, or nearer than skip_start to the sensor's, is stepped into (info[3]) but not looked up.
+ *  6 Pierce.   A visited cell that is looked up and found (lpd_loc_find; info[4]) has the surf row (c, n_c, flat_c, .).  The endpoint's
+ *              own cell is looked up once a ray and gives (c_e, n_e, flat_e) or nothing.  A row is RELIABLE iff its normal is not
+ *              (0, 0, 0) and its flatness <= max_flat.  Float64 on the fp32 values, every operation rounded once, dot products
+ *              ((a0 b0) + (a1 b1)) + (a2 b2).  The cell is pierced iff both hold:
+ *                a  the endpoint's row is not reliable, or |n_e . (c - w)| > clearance: the cell does not lie on the surface the ray
+ *                   ended on (what stops ground-grazing and wall-grazing rays);
+ *                b  the cell's row reliable: g = n_c . (o - c), h = n_c . (w - c), and (g > clearance and h < -clearance) or
+ *                   (g < -clearance and h > clearance) -- the ray crosses the cell's plane and ends well behind it;
+ *                   else: v = w - o, a = c - o, (a.a)(v.v) - (a.v)^2 < (radius radius)(v.v) -- the ray passes within radius of the
+ *                   centroid (no division, no square root).
+ *              A comparison with a NaN is false, so a NaN centroid (a slot with m <= 0) never counts.
+ * One thread a ray; the walk does not depend on the lookups, so the first probes of the next 8 cells are loaded before any chain is
+ * followed; the surf row is loaded only for a found cell.  At most 2^31 - 1 rows may be counted against one table (pierce is int32):
+ * the caller's to keep.
+ *
+ * lpd_map_carve: lpd_map_rehash with a predicate, as lpd_map_crop is.  keys_in / acc_in / capacity_in the old table and pierce
+ * [capacity_in] its counts; keys / acc / capacity the new table (cleared by the caller); min_pierce >= 1; ratio_q = rint(ratio * 1024)
+ * made on the host, 0 .. 2^20.  A cell of m rows and p pierces is MOVING iff m > 0 and p >= min_pierce and (int64) p * 1024 >=
+ * (int64) ratio_q * m (lpd_carve_moving).  Every other occupied cell goes into the new table by rule 4 of lpd_map_insert with its sums and
+ * count as they are.  info [5] int64 as lpd_map_crop's: the fifth entry counts the cells left behind.
+ *
+ * lpd_scan_moving.  The rows as lpd_map_touch takes them, the old table (keys, acc, capacity) and its pierce; min_pierce, ratio_q as
+ * above.  flags [rows] uint8: 1 for a row of the scans scan0 .. scan1-1 whose own cell (the insert's rules 1 and 2) is found and MOVING,
+ * else 0; a dropped row and a row of a chunk that is not read get 0; rows outside those scans are not written.  info [2] int64, ADDED
+ * to: rows flagged, rows not flagged.
+ */
+#define LPD_CARVE_MAX_SKIP 16              /* skip_end, skip_start: cells */
+#define LPD_CARVE_MAX_STEPS 8192           /* cells of one ray that are stepped into */
+#define LPD_CARVE_RATIO_UNITS 1024         /* ratio_q counts 1/1024ths of a cell's rows */
+#define LPD_CARVE_MAX_RATIO_Q 1048576      /* 2^20 */
+int lpd_map_pierce(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,
+                   const double* origin, float inv_cell, const long long* keys, const float* surf, long long capacity, int skip_end,
+                   int skip_start, int max_steps, float max_flat, double clearance, double radius, int32_t* pierce, long long* info,
+                   void* stream);
+int lpd_map_carve(const long long* keys_in, const long long* acc_in, long long capacity_in, const int32_t* pierce, int min_pierce, int ratio_q,
+                  long long* keys, long long* acc, long long capacity, long long* info, void* stream);
+int lpd_scan_moving(const float* points, int ld, int rows, const int32_t* offsets, const double* poses, int S, int scan0, int scan1,
+                    const double* origin, float inv_cell, const long long* keys, const long long* acc, long long capacity, const int32_t* pierce,
+                    int min_pierce, int ratio_q, unsigned char* flags, long long* info, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training path (forward in train mode + backward).  What `loss.backward()` does implicitly in the
  * reference (train_pointnetvlad.py:129,158) through BatchNorm batch statistics, LeakyReLU, the max

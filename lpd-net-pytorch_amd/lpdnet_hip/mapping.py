@@ -25,6 +25,18 @@ lap two's odometry poses in; localised poses out; lap two inserted into the same
 
 Every sum of the ICP is an integer as well, and the lookup of a cell does not depend on the slot it landed in: the localised poses are
 the same bits in every launch and at every table size, and equal tests/loc_ref.py bit for bit.
+
+Every stage above assumes a static world.  What moved through the scene is found from the rays themselves (csrc/lpd_carve.hip): every
+row is a ray from its scan's sensor position, and a cell that later rays pass straight through was not a wall.
+
+    points2, lengths2, res = mapping.remove_moving(points, lengths, poses, cell=0.5)   # the scans without the rows of moving cells
+    res.moving, res.rows_removed, res.map, res.source                          # [rows] bool, int, the carved VoxelMap, the full one
+    m.pierce(points, lengths, poses); clean = m.carved(); mask = mapping.moving_rows(m, points, lengths, poses)    # ... step by step
+
+A cell holds ONE centroid, so rows of an object that share a cell with the ground cannot be told from it: give the grid an origin
+whose z lies a little (0.1 m) above the ground, so that a cell wall separates the ground from what stands on it.  The
+walk of a ray is in integers and a count belongs to a cell's key: the same bits at every table size, batching and stream, equal to
+tests/carve_ref.py.
 """
 import numpy as np
 import torch
@@ -189,6 +201,10 @@ class VoxelMap:
         self._first_capacity = capacity
         self.keys = self.acc = self.info = None
         self._surface = None      # (reach, min_cells, surf, info): slot-indexed, so every insert and every growth drops it
+        self.pierced = None       # [capacity] int32 of pierce(): slot-indexed, so a growth drops it
+        self._pierce_state = None      # (the Carve counted with, info[0] at that time on the device, rows counted so far)
+        self.pierce_info = None   # [6] int64 of pierce()
+        self.left_behind = None   # [1] int64 on the device: the cells that carved() left behind, on the map it returned
         self.grown = 0      # doublings so far
 
     @property
@@ -211,6 +227,7 @@ class VoxelMap:
                     continue
             self.keys, self.acc, self.info = keys, acc, info
             self._surface = None
+            self.pierced = self._pierce_state = self.pierce_info = None
             self.grown += 1
             return
         raise LpdHipError(f"VoxelMap: the table cannot grow beyond {self.capacity} slots")
@@ -299,6 +316,79 @@ class VoxelMap:
             k, order = torch.sort(self.keys[live])
             s = surf[live][order]
             return SurfaceCells(s[:, 3:6].contiguous(), s[:, 6].contiguous(), s[:, 7].to(torch.int64), k, s[:, :3].contiguous())
+
+    def pierce(self, points, lengths, poses, carve=None, scans=None):
+        """Counts, per occupied cell, the rays of posed scans that pass through its content (lpd_map_pierce) and keeps the counts in
+        self.pierced ([capacity] int32, one a SLOT) and self.pierce_info ([6] int64).  points / lengths / poses / scans as insert takes
+        them -- usually the very scans that were inserted; the surface is made if needed.  Further calls with the same Carve add to the
+        same counts (one read-back: the inserted-rows counter must not have moved), and the counts per cell do not depend on how the
+        scans are split into calls; another Carve, or an insert since the counts were begun, starts over.  A growth of the table drops
+        the counts, because slots move.  PIERCE AFTER THE LAST INSERT: counts taken before a later insert into the
+        same table miss that insert's cells and rays; carved() and moving_rows() refuse them (the inserted-rows counter has moved).
+        At most 2^31 - 1 rows are counted against one table.  A first call does not wait for the device.  -> self"""
+        what = "VoxelMap.pierce"
+        carve = Carve() if carve is None else carve
+        if not isinstance(carve, Carve):
+            raise TypeError(f"{what}: carve must be a Carve, got {type(carve).__name__}")
+        if self.keys is None:
+            raise ValueError(f"{what}: nothing was inserted")
+        rows, lengths, p, a, b = _posed_input(what, points, lengths, poses, scans, self.device)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            n = int(lengths[a:b].sum())
+            fresh = self.pierced is None or self._pierce_state[0] != carve
+            if not fresh:      # counts to add to: only while nothing was inserted since they were begun (one read-back)
+                then, now = torch.cat((self._pierce_state[1], self.info[0:1])).tolist()
+                fresh = then != now
+            counted = n if fresh else self._pierce_state[2] + n
+            if counted > ops.CARVE_MAX_ROWS:
+                raise ValueError(f"{what}: {counted} rows counted against one table; at most 2^31 - 1 (the counts are int32)")
+            if fresh:
+                self.pierced = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+                self.pierce_info = torch.zeros((6,), dtype=torch.int64, device=self.device)
+            self._pierce_state = (carve, self.info[0:1].clone(), counted)
+            if n == 0 or rows.shape[0] == 0:
+                return self
+            surf = self.surface(carve.reach, carve.min_cells)
+            ops.map_pierce(rows, drive._scan_offsets(lengths, self.device), p, self.origin, self.inv_cell, self.keys, surf,
+                           carve.clearance * self.cell, carve.radius * self.cell, carve.skip_end, carve.skip_start, carve.max_steps, carve.max_flat,
+                           self.pierced, self.pierce_info, a, b)
+        return self
+
+    def _pierce_counts(self, what, carve):
+        """the counts of pierce() for the rule of `carve` (None: the Carve they were counted with) -> (pierced, carve); one read-back"""
+        if self.pierced is None:
+            raise ValueError(f"{what}: no pierce counts; call pierce() after the last insert (a growth of the table drops them)")
+        carve = self._pierce_state[0] if carve is None else carve
+        if not isinstance(carve, Carve):
+            raise TypeError(f"{what}: carve must be a Carve, got {type(carve).__name__}")
+        then, now = torch.cat((self._pierce_state[1], self.info[0:1])).tolist()      # the wait
+        if then != now:
+            raise ValueError(f"{what}: {now - then} rows were inserted after pierce(); count again after the last insert")
+        return self.pierced, carve
+
+    def carved(self, carve=None):
+        """-> a NEW VoxelMap of the same grid and capacity without the MOVING cells (lpd_map_carve): those with at least
+        carve.min_pierce pierces and carve.ratio pierces a row.  carve: None = the Carve that pierce() counted with; another one
+        applies its min_pierce and ratio to the same counts.  Its `left_behind` is the [1] int64 count of the cells that stayed
+        behind, on the device.  Waits for the device once (see pierce)."""
+        what = "VoxelMap.carved"
+        pierced, carve = self._pierce_counts(what, carve)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            out = VoxelMap(self.cell, self.origin, self.capacity, self.device)
+            cap = self.capacity
+            for _ in range(MAX_DOUBLINGS + 1):
+                out.keys, out.acc, out.info, info5 = ops.map_crop_table(cap, self.device)
+                ops.map_carve(self.keys, self.acc, pierced, carve.min_pierce, carve.ratio_q, out.keys, out.acc, info5)
+                if int(info5[2]) == 0:      # a second wait; a table that held the cells before holds fewer of them now
+                    break
+                cap *= 2
+                if cap > ops.MAP_MAX_CAPACITY:
+                    raise LpdHipError(f"{what}: the table cannot grow beyond {self.capacity} slots")
+            else:
+                raise LpdHipError(f"{what}: cells were still lost after {MAX_DOUBLINGS} doublings of the table")
+            out.info[1] = self.info[1]
+            out.left_behind = info5[4:5]
+        return out
 
 
 class SurfaceCells:
@@ -408,3 +498,93 @@ def build_map(points, lengths, poses, cell=0.2, origin=None, capacity=None, devi
     """A drive -> its VoxelMap in one call: VoxelMap(cell, origin, capacity, device).insert(points, lengths, poses).  origin=None takes
     the translation of the first finite pose."""
     return VoxelMap(cell, origin, capacity, device).insert(points, lengths, poses)
+
+
+class Carve(_Frozen):
+    """How moving objects are found in a VoxelMap, validated and frozen (lpd_map_pierce, lpd_map_carve).  skip_end,
+    skip_start: cells of a ray next to its endpoint's / the sensor's cell (Chebyshev) that are stepped into but not looked up, 0 .. 16;
+    max_steps: cells of one ray that are stepped into, 1 .. 8192; max_flat: a cell whose centroids' l3 / l2 exceeds it has no trustworthy
+    normal, in (0, 1]; clearance: how far, in CELLS, a pierced cell must lie from the plane the ray ended on, and the two ends of the ray
+    from the cell's own plane; radius: in CELLS, how near a ray must pass the centroid of a cell without a trustworthy normal; min_pierce
+    (>= 1) and ratio (pierces a row, 0 .. 1024): a cell is moving with at least min_pierce pierces and ratio pierces for every row in
+    it; reach, min_cells: VoxelMap.surface's."""
+    __slots__ = ("skip_end", "skip_start", "max_steps", "max_flat", "clearance", "radius", "min_pierce", "ratio", "reach", "min_cells")
+
+    def __init__(self, skip_end=2, skip_start=0, max_steps=ops.CARVE_MAX_STEPS, max_flat=0.15, clearance=0.3, radius=0.4, min_pierce=3, ratio=0.5,
+                 reach=1, min_cells=5):
+        what = "Carve"
+        try:
+            prm = ops.carve_ray_params(what, skip_end, skip_start, max_steps, max_flat, clearance, radius)
+            reach, min_cells = ops.map_surface_params(what, reach, min_cells)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+        for name, v in zip(("skip_end", "skip_start", "max_steps"), prm):
+            self._set(name, v)
+        self._set("max_flat", float(max_flat))
+        self._set("clearance", prm[4])
+        self._set("radius", prm[5])
+        self._set("min_pierce", self._whole(min_pierce, "min_pierce", 1, (1 << 31) - 1))
+        ops.carve_ratio_q(ratio, what)
+        self._set("ratio", float(ratio))
+        self._set("reach", reach)
+        self._set("min_cells", min_cells)
+
+    @property
+    def ratio_q(self):
+        """rint(ratio * 1024): what lpd_map_carve and lpd_scan_moving compare in integers"""
+        return ops.carve_ratio_q(self.ratio, "Carve")
+
+
+class Carving:
+    """What remove_moving returns beside the filtered scans: moving [rows] bool on the device, True for an input row that lay in a
+    moving cell (False for a row that got no cell); source = the VoxelMap of all input rows with its pierce counts; map = the carved
+    VoxelMap; rows_removed, a Python int; pierce_info [6] int64 on the device (rays traversed, rows dropped, rays cut, cells stepped
+    into, cells found, pierces counted); cells_removed: a Python int, one read-back when asked for."""
+    __slots__ = ("moving", "source", "map", "rows_removed", "pierce_info")
+
+    def __init__(self, moving, source, carved, rows_removed, pierce_info):
+        self.moving, self.source, self.map, self.rows_removed, self.pierce_info = moving, source, carved, rows_removed, pierce_info
+
+    @property
+    def cells_removed(self):
+        return 0 if self.map.left_behind is None else int(self.map.left_behind)
+
+
+def moving_rows(vmap, points, lengths, poses, carve=None, scans=None):
+    """Which rows of posed scans lie in a MOVING cell of `vmap` (lpd_scan_moving) -> [rows] bool on the device, one entry per row of the
+    concatenated input; rows of scans outside `scans`, and rows that get no cell, are False.  vmap holds the counts of VoxelMap.pierce;
+    carve: None = the Carve they were counted with.  Waits for the device once (see VoxelMap.pierce)."""
+    what = "moving_rows"
+    if not isinstance(vmap, VoxelMap):
+        raise TypeError(f"{what}: vmap must be a VoxelMap, got {type(vmap).__name__}")
+    pierced, carve = vmap._pierce_counts(what, carve)
+    rows, lengths, p, a, b = _posed_input(what, points, lengths, poses, scans, vmap.device)
+    with torch.no_grad(), torch.cuda.device(vmap.device):
+        if int(lengths[a:b].sum()) == 0 or rows.shape[0] == 0:
+            return torch.zeros((rows.shape[0],), dtype=torch.bool, device=vmap.device)
+        flags, _ = ops.scan_moving(rows, drive._scan_offsets(lengths, vmap.device), p, vmap.origin, vmap.inv_cell, vmap.keys, vmap.acc, pierced,
+                                   carve.min_pierce, carve.ratio_q, scan0=a, scan1=b)
+        return flags != 0
+
+
+def remove_moving(points, lengths, poses, cell=0.5, carve=None, origin=None, capacity=None, device=None):
+    """A drive without what moved through it: the map of all scans (build_map), its surface, the rays that pierce every cell
+    (VoxelMap.pierce), the rows that lie in a pierced cell (moving_rows), and the scans without those rows -> (points, lengths,
+    Carving).  points / lengths / poses as build_map takes them; the returned points are one concatenated tensor on the device with
+    host lengths, and go straight into drive.submaps_from_drive, build_map or odometry.estimate_poses with the same poses.  The
+    compaction is submap.filter_scans, with its one read-back."""
+    what = "remove_moving"
+    carve = Carve() if carve is None else carve
+    if not isinstance(carve, Carve):
+        raise TypeError(f"{what}: carve must be a Carve, got {type(carve).__name__}")
+    vmap = VoxelMap(cell, origin, capacity, device)
+    rows, lengths = scan_input(what, points, lengths, vmap.device)
+    vmap.insert(rows, lengths, poses)
+    if vmap.keys is None:      # no row at all
+        return rows, [int(n) for n in lengths], Carving(torch.zeros((rows.shape[0],), dtype=torch.bool, device=vmap.device), vmap, vmap, 0,
+                                                          torch.zeros((6,), dtype=torch.int64, device=vmap.device))
+    vmap.pierce(rows, lengths, poses, carve)
+    moving = moving_rows(vmap, rows, lengths, poses, carve)
+    kept, new_lengths = submap.filter_scans(rows, lengths, ~moving)
+    removed = int(sum(int(n) for n in lengths)) - int(sum(new_lengths))
+    return kept, new_lengths, Carving(moving, vmap, vmap.carved(carve), removed, vmap.pierce_info)

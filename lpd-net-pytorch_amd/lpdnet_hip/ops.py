@@ -1964,6 +1964,101 @@ def map_surface_touched(keys, acc, surf, dirty, reach=1, min_cells=5, info=None)
     return info
 
 
+# moving objects out of the drive map (csrc/lpd_carve.hip)
+CARVE_MAX_SKIP, CARVE_MAX_STEPS, CARVE_RATIO_UNITS, CARVE_MAX_RATIO_Q = _defines("CARVE", "MAX_SKIP", "MAX_STEPS", "RATIO_UNITS", "MAX_RATIO_Q")
+CARVE_MAX_ROWS = (1 << 31) - 1      # rows counted against one table: pierce is int32
+
+
+def carve_ratio_q(ratio, what="map_carve"):
+    """ratio in 0 .. 1024 pierces a row -> ratio_q = rint(ratio * 1024), half to even"""
+    top = CARVE_MAX_RATIO_Q // CARVE_RATIO_UNITS
+    if isinstance(ratio, bool) or not isinstance(ratio, numbers.Real) or not 0.0 <= float(ratio) <= float(top):
+        raise ValueError(f"{what}: ratio={ratio!r} outside 0 .. {top}")
+    return int(round(float(ratio) * CARVE_RATIO_UNITS))
+
+
+def carve_ray_params(what, skip_end, skip_start, max_steps, max_flat, clearance, radius):
+    """the host parameters of lpd_map_pierce, checked -> (skip_end, skip_start, max_steps, max_flat as fp32, clearance, radius)"""
+    skip_end = _odom_whole(what, skip_end, "skip_end", 0, CARVE_MAX_SKIP)
+    skip_start = _odom_whole(what, skip_start, "skip_start", 0, CARVE_MAX_SKIP)
+    max_steps = _odom_whole(what, max_steps, "max_steps", 1, CARVE_MAX_STEPS)
+    if isinstance(max_flat, bool) or not isinstance(max_flat, numbers.Real) or not 0.0 < float(max_flat) <= 1.0:
+        raise ValueError(f"{what}: max_flat={max_flat!r} outside (0, 1]")
+    max_flat32 = ctypes.c_float(float(max_flat)).value
+    if not 0.0 < max_flat32 <= 1.0:
+        raise ValueError(f"{what}: max_flat={max_flat!r} rounds to fp32 outside (0, 1]")
+    for v, name in ((clearance, "clearance"), (radius, "radius")):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 < float(v) < float("inf"):
+            raise ValueError(f"{what}: {name}={v!r} (metres, finite, > 0)")
+    return skip_end, skip_start, max_steps, max_flat32, float(clearance), float(radius)
+
+
+def carve_rule(what, min_pierce, ratio_q):
+    return _odom_whole(what, min_pierce, "min_pierce", 1, (1 << 31) - 1), _odom_whole(what, ratio_q, "ratio_q", 0, CARVE_MAX_RATIO_Q)
+
+
+def _map_pierce_counts(what, pierce, cap, device):
+    if pierce is None:
+        raise TypeError(f"{what}: pierce is a tensor")
+    _map_rows(what, pierce, "pierce", torch.int32, cap, None, device)
+
+
+def map_pierce(points, offsets, poses, origin, inv_cell, keys, surf, clearance, radius, skip_end, skip_start, max_steps, max_flat, pierce=None,
+               info=None, scan0=0, scan1=None):
+    """Per occupied cell of a voxel map, the rays of the scans scan0 .. scan1-1 that pass through its content (lpd_map_pierce; definition in
+    include/lpd_hip.h): points / offsets / poses / origin / inv_cell / keys / surf as map_localize takes them; clearance and radius in
+    METRES; skip_end, skip_start in cells; no defaults here: mapping.Carve holds the one set -> (pierce [capacity] int32, one count a SLOT; info [6] int64 = rays traversed, rows dropped,
+    rays cut at max_steps, cells stepped into, cells found, pierces counted).  A given pierce / info is added to.  Nothing is read back."""
+    what = "map_pierce"
+    h = _PosedScans(what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1)
+    _map_surf(what, surf, h.cap, keys.device)
+    prm = carve_ray_params(what, skip_end, skip_start, max_steps, max_flat, clearance, radius)
+    if pierce is None:
+        pierce = _zeros((h.cap,), torch.int32, keys.device)
+    _map_pierce_counts(what, pierce, h.cap, keys.device)
+    info = _counters(what, info, 6, torch.int64, keys.device)
+    _call("map_pierce", _lib.load().lpd_map_pierce, *h.table, _ptr(h.poses), *h.scans, *h.grid, _ptr(keys), _ptr(surf), h.cap, *prm, _ptr(pierce),
+          _ptr(info), _stream())
+    return pierce, info
+
+
+def map_carve(keys_in, acc_in, pierce, min_pierce, ratio_q, keys, acc, info5):
+    """The cells of one table that are not MOVING into another, cleared one (lpd_map_carve): pierce [capacity_in] int32 from map_pierce;
+    a cell of m rows and p pierces is moving iff p >= min_pierce and p * 1024 >= ratio_q * m (ratio_q = carve_ratio_q(ratio)); info5
+    [5] int64 is added to (rows, -, rows lost, cells created, cells left behind; map_crop_table makes one).  Nothing is read back."""
+    what = "map_carve"
+    if info5 is None:
+        raise ValueError(f"{what}: info5 must be a contiguous [5] int64 tensor")
+    cap_in, cap = _map_two_tables(what, keys_in, acc_in, keys, acc)
+    _map_pierce_counts(what, pierce, cap_in, keys.device)
+    _counters(what, info5, 5, torch.int64, keys.device, "info5", make=False)
+    min_pierce, ratio_q = carve_rule(what, min_pierce, ratio_q)
+    _call("map_carve", _lib.load().lpd_map_carve, _ptr(keys_in), _ptr(acc_in), cap_in, _ptr(pierce), min_pierce, ratio_q, _ptr(keys), _ptr(acc), cap,
+          _ptr(info5), _stream())
+
+
+def scan_moving(points, offsets, poses, origin, inv_cell, keys, acc, pierce, min_pierce, ratio_q, flags=None, info=None, scan0=0, scan1=None):
+    """Which rows of the scans scan0 .. scan1-1 lie in a MOVING cell (lpd_scan_moving): the rows as map_touch takes them, the table and
+    its pierce counts -> (flags [rows] uint8: 1 for a row whose own cell is found and moving, else 0 -- rows outside those scans keep
+    what a given flags held, 0 in a new one; info [2] int64 = rows flagged, rows not flagged; a given info is added to).  Nothing is
+    read back."""
+    what = "scan_moving"
+    h = _PosedScans(what, points, offsets, poses, origin, inv_cell, keys, scan0, scan1)
+    _map_acc(what, acc, h.cap, keys.device)
+    _map_pierce_counts(what, pierce, h.cap, keys.device)
+    min_pierce, ratio_q = carve_rule(what, min_pierce, ratio_q)
+    n = points.shape[0]
+    if flags is None:
+        flags = _zeros((n,), torch.uint8, keys.device)
+    _req(flags, "flags", torch.uint8)
+    if tuple(flags.shape) != (n,) or not flags.is_contiguous() or flags.device != keys.device:
+        raise ValueError(f"{what}: flags must be a contiguous [rows] = ({n},) uint8 tensor on {keys.device}, got {tuple(flags.shape)}")
+    info = _counters(what, info, 2, torch.int64, keys.device)
+    _call("scan_moving", _lib.load().lpd_scan_moving, *h.table, _ptr(h.poses), *h.scans, *h.grid, _ptr(keys), _ptr(acc), h.cap, _ptr(pierce),
+          min_pierce, ratio_q, _ptr(flags), _ptr(info), _stream())
+    return flags, info
+
+
 # motion compensation of LiDAR sweeps (csrc/lpd_deskew.hip, lpd_odom_motion in csrc/lpd_odom.hip)
 def deskew_ref(ref, what="scan_deskew"):
     """the reference time of a sweep, a real number in 0 .. 1 -> float"""
